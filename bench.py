@@ -1,8 +1,15 @@
 """Headline benchmark: SVDFormer PCN train-step samples/s on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, the K timed
+steps, the outputs of the last timed step as DIR/<name>.npy (--dump-outputs) and the result line
+(metric, value, unit, higher_is_better, dtype, ms_per_step and the run's configuration).  Every
+other measurement below -- per-kernel HIP-event timing and the roofline fields built from it, the
+idle-GPU issue cost, the configs[1] fp32 leg, the fp32 and PointSea train steps, EMD, the CPU
+baseline, the detail file -- runs with --full only.
 
 One step = one iteration of core/train_pcn.py:101-134 on a synthetic
 PCN-shaped batch resident in HBM: depth render of the partial cloud
@@ -15,7 +22,7 @@ libpcops.so (hand-written gfx950 HIP); dense layers are torch (MIOpen /
 hipBLASLt).  N>1: one process per GPU, batch-partitioned (weak scaling),
 gradients all-reduced over RCCL by DDP -- the only data-path collective.
 
-Rank 0 prints ONE JSON line (the driver's contract, kept under 8 KB: `compact`) with, in addition:
+Rank 0 prints ONE JSON line (the driver's contract, kept under 8 KB: `compact`) with, under --full, in addition:
   roofline      -- the dominant libpcops op (the attention core, all passes): algorithmic FLOP per
                    launch / mean launch duration, HIP events on the launch stream (DESIGN.md 4);
   cpu_baseline  -- the same train step on the host CPU for a bounded sample
@@ -57,6 +64,13 @@ def parse():
                          "train step with the PCViews_Real renderer (configs[4])")
     ap.add_argument("--batch", type=int, default=None, help="samples per GPU (32 PCN, 16 ShapeNet-55)")
     ap.add_argument("--fp32", action="store_true", help="no bf16 autocast (configs[1] numerics)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline: per-kernel timing + roofline, idle-GPU "
+                         "issue cost, the fp32 / PointSea / EMD legs, the CPU baseline, the detail file (each can "
+                         "still be switched off by its own --no-* option); without it only the headline is timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the loss and its three Chamfer terms) to "
+                         "DIR/<name>.npy as float32 (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fp32-leg", action="store_true",
                     help="skip the configs[1] figure (fp32 forward + loss, B=16) reported beside the bf16 step")
@@ -683,11 +697,15 @@ class Workload:
         from svdformer_pointsea_amd.metrics import gt_pyramid
         return gt_pyramid(gt, 2048, 256)
 
-    def loss(self, pcds, partial, gt, gts=None):
+    def losses(self, pcds, partial, gt, gts=None):
+        """(total, [coarse, fine1, fine2 Chamfer terms]) as the reference's train loops receive them."""
         from svdformer_pointsea_amd.metrics import get_loss, get_loss_PM
         if self.name == "svdformer":
-            return get_loss(pcds, gt, sqrt=True, gts=gts)[0]
-        return get_loss_PM(pcds, partial, gt, sqrt=False, gts=gts)[0]
+            return get_loss(pcds, gt, sqrt=True, gts=gts)
+        return get_loss_PM(pcds, partial, gt, sqrt=False, gts=gts)
+
+    def loss(self, pcds, partial, gt, gts=None):
+        return self.losses(pcds, partial, gt, gts)[0]
 
 
 # ------------------------------------------------------------------ CPU baseline
@@ -927,6 +945,23 @@ class Leg:
     captured graphs, timings)."""
 
 
+def host_outputs(loss, terms):
+    """The train step's outputs as float32 numpy arrays by file name: the total loss and its
+    Chamfer terms (coarse, fine1, fine2), as core/train_pcn.py:113 / train_55.py:159 receive them
+    from get_loss / get_loss_PM.  The predicted clouds are not written: they are no repeatable
+    function of the inputs."""
+    return {"loss": loss.float().reshape(1).cpu().numpy(),
+            "loss_terms": torch.stack([t.float().reshape(()) for t in terms]).cpu().numpy()}
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def train_leg(args, wl, batch, amp, steps, warmup, device, world, rank, use_dist, kernel_timing, tag):
     """Build wl's model, warm up, capture the step into HIP graphs (unless
     --no-graph) and time `steps` steps between barrier + synchronize pairs.
@@ -944,6 +979,7 @@ def train_leg(args, wl, batch, amp, steps, warmup, device, world, rank, use_dist
     # weights refreshed by one cast per step (svdformer_pointsea_amd/train.py)
     fp = L.fp = FlatParams(model, device, bf16=amp)
     use_graph = L.use_graph = not args.no_graph
+    keep_outputs = bool(args.dump_outputs) and tag == "headline"
     # one parameter group, elementwise update: Adam over the flat master buffer;
     # the LR is a device tensor so the captured optimizer graph reads the value
     # the schedule writes each step (warm-up per batch, train_pcn.py:132-134)
@@ -991,7 +1027,7 @@ def train_leg(args, wl, batch, amp, steps, warmup, device, world, rank, use_dist
         depth = wl.images(inp)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp, cache_enabled=not use_graph):
             pcds = fp.forward(inp, depth)
-            loss = wl.loss(pcds, inp, gt, br.join(*gts))
+            loss, terms = wl.losses(pcds, inp, gt, br.join(*gts))
         loss.backward()
         if sync[0] is not None:
             sync[0].finish()   # the bucketed all-reduces were issued during backward
@@ -1000,6 +1036,10 @@ def train_leg(args, wl, batch, amp, steps, warmup, device, world, rank, use_dist
         if prefetch:
             staged[0].copy_(bn.join(nxt))
         loss_acc.add_(loss.detach())  # logged without a host sync
+        if keep_outputs:
+            # what a caller of the step receives; captured, these are the graph's own static
+            # buffers and hold the values of the latest replay
+            L.outputs = (loss.detach(), [t.detach() for t in terms])
 
     def grad_sync():
         if use_dist and sync[0] is None:
@@ -1127,8 +1167,10 @@ def train_leg(args, wl, batch, amp, steps, warmup, device, world, rank, use_dist
         torch.cuda._sleep(1000)
         torch.cuda.synchronize()
     check_finite("the timed steps")
+    # the last timed step's outputs leave the device here: the steps below overwrite them
+    L.dump = host_outputs(*L.outputs) if keep_outputs else None
     L.idle_issue_ms = None
-    if use_graph:
+    if use_graph and args.full:
         # host cost of issuing one step's graph replays against an IDLE GPU: separates
         # the graph-launch cost of ~1.5 k nodes from queue back-pressure in host_issue
         # (these replays are extra train steps, outside the clock)
@@ -1206,9 +1248,23 @@ def extra_leg(args, name, batch, amp, device, steps):
     return out
 
 
+def write_detail(args, out):
+    """The full per-kernel tables of every leg: to the detail file and to stderr."""
+    detail = args.detail_json or os.path.join(ROOT, "profiles", f"bench_detail_{time.strftime('%Y%m%d_%H%M%S')}.json")
+    try:
+        os.makedirs(os.path.dirname(detail), exist_ok=True)
+        with open(detail, "w") as f:
+            json.dump(out, f, indent=1)
+    except OSError as exc:
+        progress(f"detail file not written ({exc})")
+    print("[bench detail] " + json.dumps(out), file=sys.stderr, flush=True)
+
+
 def main():
     global _RESULT_FD
     args = parse()
+    if not args.full:   # a plain run times the headline only
+        args.no_kernel_timing = args.no_fp32_leg = args.no_extra_legs = args.no_cpu_baseline = True
     if args.visited_json and os.path.exists(args.visited_json):
         kernel_table.visited = {k: v["visited_frac"] for k, v in json.load(open(args.visited_json)).items()}
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1253,6 +1309,8 @@ def main():
     use_graph, host_ms, nparams = leg.use_graph, leg.host * 1e3 / args.steps, leg.nparams
     idle_issue_ms = leg.idle_issue_ms
     optimizer_impl = leg.optimizer_impl
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, leg.dump)
 
     fp32_leg = None
     extra = {}
@@ -1291,7 +1349,8 @@ def main():
                           if sync is not None else "one all-reduce of the flat bucket after backward"),
             "gemm_selection": (f"TunableOp ({args.tunableop}): {os.path.relpath(tuned, ROOT)}" if tuned
                                else "hipBLASLt heuristics"),
-            "kernel_timing": ("HIP events per libpcops launch, %d eager steps after the timed graph replays"
+            "kernel_timing": "off" if args.no_kernel_timing else
+                             ("HIP events per libpcops launch, %d eager steps after the timed graph replays"
                               % args.timing_steps) if use_graph else "HIP events per libpcops launch, timed steps",
             "higher_is_better": True,
             "scaling": "weak",
@@ -1315,14 +1374,8 @@ def main():
             progress(f"timed {out['ms_per_step']:.2f} ms/step; CPU baseline")
             out["cpu_baseline"] = cpu_baseline(wl, args.cpu_steps)
         # the full per-kernel tables go to a detail file and to stderr; stdout carries the compact line
-        detail = args.detail_json or os.path.join(ROOT, "profiles", f"bench_detail_{time.strftime('%Y%m%d_%H%M%S')}.json")
-        try:
-            os.makedirs(os.path.dirname(detail), exist_ok=True)
-            with open(detail, "w") as f:
-                json.dump(out, f, indent=1)
-        except OSError as exc:
-            progress(f"detail file not written ({exc})")
-        print("[bench detail] " + json.dumps(out), file=sys.stderr, flush=True)
+        if args.full:
+            write_detail(args, out)
         line = compact(out) + "\n"
         if _RESULT_FD is not None:
             sys.stdout.flush()

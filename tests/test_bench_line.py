@@ -125,6 +125,32 @@ def test_oversized_line_drops_optional_fields():
     assert len(line.encode()) < 8192 and "roofline" in json.loads(line)
 
 
+def test_full_and_dump_outputs_options(monkeypatch):
+    """--full is off by default (a plain run times the headline only); --dump-outputs takes the directory."""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None and (args.steps, args.warmup) == (7, 2)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "out"
+
+
+def test_dump_outputs_names_and_dtype(tmp_path):
+    """--dump-outputs: the step's total loss and its three Chamfer terms as float32 <name>.npy."""
+    import numpy as np
+    import torch
+
+    terms = [torch.tensor(v, dtype=torch.bfloat16) for v in (0.125, 0.0625, 0.03125)]
+    loss = terms[0] + terms[1] + terms[2]
+    out = bench.host_outputs(loss, terms)
+    assert list(out) == ["loss", "loss_terms"] and all(a.dtype == np.float32 for a in out.values())
+    assert out["loss"].shape == (1,) and out["loss"][0] == 0.21875
+    assert out["loss_terms"].tolist() == [0.125, 0.0625, 0.03125]
+    bench.write_outputs(str(tmp_path / "d"), out)
+    assert sorted(os.listdir(tmp_path / "d")) == ["loss.npy", "loss_terms.npy"]
+    assert np.array_equal(np.load(tmp_path / "d" / "loss_terms.npy"), out["loss_terms"])
+
+
 def test_layernorm_bwd_work_models_both_layouts():
     """The LayerNorm backward's byte model reads the argument layout of the entry point that ran: the
     round-6 pcops_layernorm_bwd_ex (23 args, dy first with its dtype, stride and the extra gradient) and

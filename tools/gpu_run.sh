@@ -6,9 +6,9 @@
 #   tests_k      pytest -m gpu -k "$PYTEST_K"
 #   smoke        __graft_entry__.smoke()
 #   probe        tools/valu_probe (VALU issue cost per instruction kind)
-#   bench        bench.py default line (PCN, N=1)
-#   bench_ps     bench.py --model pointsea
-#   bench_fp32   bench.py --fp32 --batch 16 (configs[1] numerics)
+#   bench        bench.py --full line (PCN, N=1, every leg)
+#   bench_ps     bench.py --full --model pointsea
+#   bench_fp32   bench.py --full --fp32 --batch 16 (configs[1] numerics)
 #   trace        rocprofv3 --kernel-trace --stats of bench.py
 #   pmc_traffic  two PMC passes (FETCH_SIZE / WRITE_SIZE) -> tools/pmc_traffic.py
 #   pmc_attn     SQ counter pass over the attention kernels (tools/attn_bench.py)
@@ -31,16 +31,16 @@ run_stage() {
              -k "${PYTEST_K:?set PYTEST_K}" > "$OUT/pytest_gpu_k.log" 2>&1 ;;
     smoke) timeout -k 10 300 python -u -c 'import __graft_entry__ as g; g.smoke()' > "$OUT/smoke.log" 2>&1 ;;
     probe) timeout -k 10 60 ./tools/valu_probe > "$OUT/valu_probe.txt" 2>&1 ;;
-    bench) timeout -k 10 600 python bench.py --detail-json "$OUT/bench_detail.json" ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
-    bench_ps) timeout -k 10 500 python bench.py --model pointsea --detail-json "$OUT/bench_ps_detail.json" > "$OUT/bench_pointsea.json" 2> "$OUT/bench_pointsea.err" ;;
-    bench_sa) PCOPS_CONV1X1=sa timeout -k 10 600 python bench.py --no-cpu-baseline --no-fp32-leg > "$OUT/bench_sa.json" \
+    bench) timeout -k 10 600 python bench.py --full --detail-json "$OUT/bench_detail.json" ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err" ;;
+    bench_ps) timeout -k 10 500 python bench.py --full --model pointsea --detail-json "$OUT/bench_ps_detail.json" > "$OUT/bench_pointsea.json" 2> "$OUT/bench_pointsea.err" ;;
+    bench_sa) PCOPS_CONV1X1=sa timeout -k 10 600 python bench.py --full --no-cpu-baseline --no-fp32-leg > "$OUT/bench_sa.json" \
              2> "$OUT/bench_sa.err" ;;
-    bench_ps_sa) PCOPS_CONV1X1=sa timeout -k 10 500 python bench.py --model pointsea --no-cpu-baseline \
+    bench_ps_sa) PCOPS_CONV1X1=sa timeout -k 10 500 python bench.py --full --model pointsea --no-cpu-baseline \
              > "$OUT/bench_pointsea_sa.json" 2> "$OUT/bench_pointsea_sa.err" ;;
-    bench_fp32) timeout -k 10 500 python bench.py --fp32 --batch 16 --no-cpu-baseline > "$OUT/bench_fp32.json" \
+    bench_fp32) timeout -k 10 500 python bench.py --full --fp32 --batch 16 --no-cpu-baseline > "$OUT/bench_fp32.json" \
                   2> "$OUT/bench_fp32.err" ;;
     trace) PCOPS_TRACE_MARKS=1 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
-             python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-fp32-leg --no-extra-legs \
+             python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-fp32-leg --no-extra-legs \
              > "$OUT/bench_traced.json" 2> "$OUT/trace.err"
            rc=$?
            [ $rc -eq 0 ] && python tools/trace_window.py "$(find "$OUT/trace" -name '*kernel_trace.csv' -print -quit)" 10 \
@@ -55,7 +55,7 @@ run_stage() {
         trace_ps) mk=1; tw=10; bargs="--model pointsea --steps 10 --warmup 3" ;;
       esac
       PCOPS_TRACE_MARKS=$mk timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/$1" -o run -- \
-        python bench.py $bargs --no-cpu-baseline > "$OUT/$1.json" 2> "$OUT/$1.err"
+        python bench.py --full $bargs --no-cpu-baseline > "$OUT/$1.json" 2> "$OUT/$1.err"
       rc=$?
       [ $rc -eq 0 ] && python tools/trace_window.py "$(find "$OUT/$1" -name '*kernel_trace.csv' -print -quit)" $tw \
         "$OUT/${1}_kernel_stats_replay.csv" > "$OUT/${1}_window.txt" 2>&1
@@ -122,7 +122,7 @@ run_stage() {
       python tools/attn_variant.py cmp "$OUT/av_base.pt" "$OUT/av_new.pt" >> "$OUT/attn_lib_cmp.txt" 2>&1
       rc=$?; rm -f "$OUT"/av_*.pt; return $rc ;;
     dist1) timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 \
-             --master-port 29611 bench.py --dist-selftest --steps 5 --warmup 2 --no-cpu-baseline --no-fp32-leg --no-extra-legs \
+             --master-port 29611 bench.py --full --dist-selftest --steps 5 --warmup 2 --no-cpu-baseline --no-fp32-leg --no-extra-legs \
              > "$OUT/bench_dist1.json" 2> "$OUT/bench_dist1.err" ;;
     pmc_attn2)
       timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS \

@@ -186,6 +186,44 @@ int pcops_chamfer_backward(const float *xyz1, const float *xyz2, int B, int N, i
 int pcops_chamfer_sqrt_mean_grad(const float *grad_out, float scale, const float *s1, long long n1, const float *s2,
                                  long long n2, float *gd1, float *gd2, pcops_stream_t stream);
 
+/* ---------------- Completion metrics (utils/loss_utils.py:98-155, metrics/CD/fscore.py:3-16) ----------------
+ * pcops_completion_metrics: what calc_cd(output, gt, calc_f1=True) and calc_dcd(output, gt, alpha, n_lambda=1)
+ * compute per sample from ONE Chamfer result chamfer(gt, output), in one launch.
+ *   dist1 (B,N) fp32 squared, idx1 (B,N) int32 in [0,M): every gt point's nearest output point;
+ *   dist2 (B,M) fp32 squared, idx2 (B,M) int32 in [0,N): every output point's nearest gt point.
+ *   An index outside its range counts no hit and reads a hit count of 0; it is never dereferenced.
+ *   threshold: the F-score's (strict `<`, so NaN is not below); alpha: the density term's;
+ *   frac1 / frac2: the density weights' factors of direction 1 / 2 (calc_dcd's frac_21 = N / M and
+ *   frac_12 = M / N, or max(1, .) of them under non_reg -- the caller's choice).
+ *   out (B, PCOPS_METRICS_COLS) fp32, fully written, columns below; with mean(x) = sum(x) * (1.0f / n),
+ *   as torch's GPU mean:
+ *     hits(i)  = the number of the direction's points that share point i's index
+ *     term     = mean(1 - expf(-d * alpha) * (1 / ((float)hits + 1e-6f) * frac))
+ *     p        = (float)count(d < threshold) * (1.0f / n)
+ *     f1       = 2 * p1 * p2 / (p1 + p2), 0 where that is NaN
+ *   A row depends on its own sample only and is the same bits on every run (fixed summation order:
+ *   per thread serially with stride 1024, lanes by the xor butterfly, waves in index order).
+ * workspace: pcops_completion_metrics_workspace_bytes(B,N,M) bytes: 0 while max(N,M) <= 32768 (the hit
+ *   counts live in LDS), else B * max(N,M) * 4 (zeroed by the kernel; a NULL or short workspace then
+ *   returns PCOPS_ERR_WORKSPACE without launching).  B, N or M <= 0 returns PCOPS_ERR_INVALID. */
+#define PCOPS_METRICS_L1A 0   /* mean(sqrt(dist1)) */
+#define PCOPS_METRICS_L1B 1   /* mean(sqrt(dist2)) */
+#define PCOPS_METRICS_L2A 2   /* mean(dist1) */
+#define PCOPS_METRICS_L2B 3   /* mean(dist2) */
+#define PCOPS_METRICS_CD_P 4  /* (l1a + l1b) / 2 */
+#define PCOPS_METRICS_CD_T 5  /* l2a + l2b */
+#define PCOPS_METRICS_P1 6    /* precision_1: dist1 below the threshold */
+#define PCOPS_METRICS_P2 7    /* precision_2: dist2 below the threshold */
+#define PCOPS_METRICS_F1 8
+#define PCOPS_METRICS_T1 9    /* density term of direction 1 */
+#define PCOPS_METRICS_T2 10   /* density term of direction 2 */
+#define PCOPS_METRICS_DCD 11  /* (t1 + t2) / 2 */
+#define PCOPS_METRICS_COLS 12
+unsigned long long pcops_completion_metrics_workspace_bytes(int B, int N, int M);
+int pcops_completion_metrics(const float *dist1, const int *idx1, const float *dist2, const int *idx2, int B, int N,
+                             int M, float threshold, float alpha, float frac1, float frac2, float *out,
+                             void *workspace, unsigned long long workspace_bytes, pcops_stream_t stream);
+
 /* ---------------- 3x3 / stride 2 / pad 1 max pool (torchvision resnet stem, PointSea ResEncoder)
  * pcops_maxpool3s2_fwd: nn.MaxPool2d(3, 2, 1) on a channels_last (N, H, W, C) activation (dtype 0
  * fp32, 1 bf16) -> y (N, ceil(H/2), ceil(W/2), C) and each output's winning window offset (uint8,

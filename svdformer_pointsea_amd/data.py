@@ -62,7 +62,7 @@ def _crop_pack(dist, xyz, start, count, n_max):
 
 
 def seprate_point_cloud(xyz, num_points, crop, fixed_points=None, padding_zeros=False, generator=None,
-                        want_crop=True):
+                        want_crop=True, centers=None):
     """utils/helpers.py:62-123 -> (input_data, crop_data).
 
     crop: int, or [lo, hi] for a per-sample random crop size (then both parts
@@ -72,7 +72,10 @@ def seprate_point_cloud(xyz, num_points, crop, fixed_points=None, padding_zeros=
     reference's global `random` / `torch.randn` draws for reproducible runs.
     want_crop=False returns (input_data, None) without the crop part's FPS: the
     train loop discards it (core/train_55.py:150 `partial, _ = ...`), FPS draws
-    no random numbers, so input_data is unchanged."""
+    no random numbers, so input_data is unchanged.
+    centers (optional, a (B, 3) tensor): sample b's crop centre, instead of a draw or of
+    fixed_points -- the ShapeNet-55 test protocol's fixed viewpoints for a whole batch of
+    (shape, view) pairs at once (core/test_55.py:71-72 calls this per view at B = 1)."""
     B, n, c = xyz.shape
     assert n == num_points
     assert c == 3
@@ -86,7 +89,9 @@ def seprate_point_cloud(xyz, num_points, crop, fixed_points=None, padding_zeros=
             num_crop = torch.randint(crop[0], crop[1] + 1, (B,), device=dev, generator=generator)
     else:
         num_crop = torch.full((B,), int(crop), device=dev)
-    if fixed_points is None:
+    if centers is not None:
+        center = torch.as_tensor(centers, dtype=xyz.dtype).reshape(B, 1, 3).to(dev)
+    elif fixed_points is None:
         if generator is None:
             center = F.normalize(torch.randn(B, 1, 3), p=2, dim=-1).to(dev)
         else:

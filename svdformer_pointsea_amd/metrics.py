@@ -6,11 +6,14 @@ utils/loss_utils.py:10-155 and metrics/CD/fscore.py:3-16.
   calc_cd                                                CD-L1 (cd_p), CD-L2 (cd_t), F-score
   calc_dcd                                               density-aware Chamfer
   fscore                                                 F-score on squared distances
+  completion_metrics(_raw)                               all of the last three from one Chamfer search,
+                                                         in one launch (csrc/metrics.hip)
 Names, arguments and return structures are the reference's.  The
 nearest-neighbour search is the Chamfer kernel (csrc/chamfer.hip, both
 directions in one launch); what follows it are the same reductions, in the
 same floating-point order, as the reference's torch expressions.
 """
+import collections
 import os
 
 import torch
@@ -18,7 +21,7 @@ from torch.amp import custom_bwd, custom_fwd
 from torch.autograd import Function
 
 from . import chamfer3D
-from ._lib import call, lib, ptr, stream_of
+from ._lib import Workspace, call, lib, ptr, require_float, require_int, stream_of
 from .model_utils import fps_subsample
 
 _nn = chamfer3D.chamfer_3DDist()
@@ -178,3 +181,61 @@ def calc_dcd(x, gt, alpha=1000, n_lambda=1, return_raw=False, non_reg=False):
     if return_raw:
         res.extend([dist1, dist2, idx1, idx2])
     return res
+
+
+# column layout of pcops_completion_metrics' output row (include/pcops.h PCOPS_METRICS_*)
+_METRIC_COLS = ("l1a", "l1b", "l2a", "l2b", "cd_p", "cd_t", "p1", "p2", "f1", "t1", "t2", "dcd")
+CompletionMetrics = collections.namedtuple("CompletionMetrics", _METRIC_COLS)
+CompletionMetrics.__doc__ = """Per-sample (B,) tensors: cd_p (CD-L1), cd_t (CD-L2), f1, dcd, and their parts --
+l1a / l1b = mean(sqrt(dist1 / dist2)), l2a / l2b = mean(dist1 / dist2), p1 / p2 the F-score's two
+precisions, t1 / t2 the two density terms (direction 1 is gt -> output, as calc_cd)."""
+
+
+def _dcd_fracs(n_x, n_gt, non_reg):
+    f12, f21 = n_x / n_gt, n_gt / n_x
+    return (max(1, f12), max(1, f21)) if non_reg else (f12, f21)
+
+
+def completion_metrics_raw(dist1, dist2, idx1, idx2, threshold=1e-4, alpha=1000, non_reg=False):
+    """CompletionMetrics of one Chamfer result chamfer(gt, output) -- dist1 / idx1 (B, n_gt), dist2 / idx2
+    (B, n_out), CUDA fp32 / int32 -- in one launch (pcops_completion_metrics, n_lambda == 1).  The
+    fields are column views of the kernel's (B, 12) output: no torch arithmetic follows the launch."""
+    for t, name in ((dist1, "dist1"), (dist2, "dist2")):
+        require_float(t, name)
+    for t, name in ((idx1, "idx1"), (idx2, "idx2")):
+        require_int(t, name)
+    B, n = dist1.shape
+    m = dist2.shape[1]
+    if dist2.shape[0] != B or idx1.shape != dist1.shape or idx2.shape != dist2.shape:
+        raise RuntimeError("completion_metrics_raw: dist1 / idx1 must be (B, n_gt) and dist2 / idx2 (B, n_out)")
+    f12, f21 = _dcd_fracs(m, n, non_reg)
+    dev = dist1.device
+    out = torch.empty(B, len(_METRIC_COLS), device=dev)
+    with torch.cuda.device(dev):
+        wsb = lib().pcops_completion_metrics_workspace_bytes(B, n, m)
+        ws = Workspace.get(dev, wsb)
+        call("completion_metrics", lib().pcops_completion_metrics, ptr(dist1), ptr(idx1), ptr(dist2), ptr(idx2), B, n,
+             m, threshold, alpha, f21, f12, ptr(out), ptr(ws), wsb, stream_of(dist1))
+    return CompletionMetrics(*out.unbind(1))
+
+
+def completion_metrics(output, gt, threshold=1e-4, alpha=1000, n_lambda=1, non_reg=False):
+    """calc_cd(output, gt, calc_f1=True) and calc_dcd(output, gt, alpha, n_lambda, non_reg=non_reg) as one
+    CompletionMetrics: one Chamfer search (the reference runs it twice, calc_dcd calls calc_cd again) and
+    one pcops_completion_metrics launch instead of ~50 scalar / elementwise ones.  Inputs that are not
+    CUDA fp32, or n_lambda != 1, compose the existing calc_cd / calc_dcd (so under oracle.cpu_path.cpu_ops()
+    it runs on the CPU)."""
+    if (n_lambda == 1 and output.is_cuda and gt.is_cuda and output.dtype == torch.float32
+            and gt.dtype == torch.float32):
+        dist1, dist2, idx1, idx2 = chamfer3D.chamfer_forward_raw(gt.detach().contiguous(),
+                                                                 output.detach().contiguous())
+        return completion_metrics_raw(dist1, dist2, idx1, idx2, threshold, alpha, non_reg)
+    with torch.no_grad():
+        output, gt = output.float(), gt.float()
+        l1, l2, dist1, dist2, idx1, idx2 = calc_cd(output, gt, return_raw=True, separate=True)
+        f1, p1, p2 = fscore(dist1, dist2, threshold)
+        f12, f21 = _dcd_fracs(output.shape[1], gt.shape[1], non_reg)
+        t1 = _density_term(dist1.float(), idx1, output.shape[1], alpha, n_lambda, f21)
+        t2 = _density_term(dist2.float(), idx2, gt.shape[1], alpha, n_lambda, f12)
+        return CompletionMetrics(l1[0], l1[1], l2[0], l2[1], (l1[0] + l1[1]) / 2, l2[0] + l2[1], p1, p2, f1, t1, t2,
+                                 (t1 + t2) / 2)

@@ -9,7 +9,8 @@
  *     frees or synchronises, so callers may capture it into a hipGraph;
  *   - outputs are fully written (the reference zero-initialises them in
  *     C++/Python -- sampling.cpp:25-27, dist_chamfer_3D.py:33-42,56-60 -- so
- *     "zero + accumulate" outputs are zeroed here with hipMemsetAsync);
+ *     "zero + accumulate" outputs are zeroed here, by a fill kernel on
+ *     `stream`: a captured hipMemsetAsync node replays wrongly);
  *   - scratch is caller-provided through `workspace` (size from the matching
  *     *_workspace_bytes query);
  *   - the return value is a status code (PCOPS_OK == 0).  The reference
@@ -504,6 +505,26 @@ int pcops_batchnorm_bwd(const void *dy, const void *y, const void *x, int dtype,
                         const float *gamma, const float *save_mean, const float *save_invstd, int batch_stats, int act,
                         float slope, void *dx, void *dres, float *dgamma, float *dbeta, void *workspace,
                         unsigned long long workspace_bytes, pcops_stream_t stream);
+/* pcops_batchnorm_fwd_save / pcops_batchnorm_bwd_saved: the same forward and backward (same reference
+ *   lines, bitwise the same results) with the backward's two passes no longer reading y to learn
+ *   whether each element passed the activation.
+ *   _fwd_save also writes save_coef (required, fp32, 2*C: the per-channel scale and shift of
+ *   y = act(x * scale + shift (+ res))) and, when save_mask is given, one bit per element of y
+ *   (rows*C/8 bytes; bit k of byte v: element 8*v + k passed the activation, judged on y as stored).
+ *   _bwd_saved takes the decision from save_mask when it is given, else recomputes y from x and
+ *   save_coef with the forward's own expression and rounding -- valid only for a forward without
+ *   `res`; act = 0 needs neither.  Everything else as pcops_batchnorm_fwd / _bwd, same workspace. */
+int pcops_batchnorm_fwd_save(const void *x, int dtype, const void *res, int res_dtype, long long rows, int C,
+                             const float *gamma, const float *beta, float *running_mean, float *running_var,
+                             float momentum, float eps, int batch_stats, int act, float slope, void *y,
+                             float *save_mean, float *save_invstd, float *save_coef, unsigned char *save_mask,
+                             void *workspace, unsigned long long workspace_bytes, long long *num_batches_tracked,
+                             pcops_stream_t stream);
+int pcops_batchnorm_bwd_saved(const void *dy, const float *save_coef, const unsigned char *save_mask, const void *x,
+                              int dtype, long long rows, int C, const float *gamma, const float *save_mean,
+                              const float *save_invstd, int batch_stats, int act, float slope, void *dx, void *dres,
+                              float *dgamma, float *dbeta, void *workspace, unsigned long long workspace_bytes,
+                              pcops_stream_t stream);
 
 /* ---------------- 3x3 convolution, stride 1, pad 1, no bias, on channels_last bf16 ----------------
  * The ResNet BasicBlock convs of SVDFormer's image encoder (models/resnet.py:36-70 via

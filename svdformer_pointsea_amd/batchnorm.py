@@ -11,6 +11,13 @@ The modules stay nn.BatchNorm2d (state_dict, running statistics and
 num_batches_tracked as torch keeps them); only their forward is replaced.
 torch's MIOpen path runs a BasicBlock's bn2 + add + relu as five full passes
 over the activation forward and six backward; here it is two and two.
+
+The backward's two passes do not read the forward output to learn which
+elements passed the activation: without a residual they recompute it from x and
+the forward's saved per-channel (scale, shift), bit for bit as the forward
+stored it (PCOPS_BN_RECOMPUTE_MASK=0: read y); with a residual the forward
+leaves one bit per element in a tensor of its own (PCOPS_BN_MASK_BITS=0: read
+y).  Both give bitwise the gradients of the y-reading form.
 """
 import os
 
@@ -30,6 +37,22 @@ def _rows_c(x):
     return x.numel() // C, C
 
 
+def _switch(name):
+    return os.environ.get(name, "1") != "0"
+
+
+def _mask_source(act, has_res):
+    """Where the backward takes the activation's decision from: "coef" (recomputed from x and the
+    forward's scale / shift: PCOPS_BN_RECOMPUTE_MASK, forward without a residual), "bits" (one saved
+    bit per element: PCOPS_BN_MASK_BITS, forward with a residual) or "y" (the forward output).
+    Both switches are read per call, as PCOPS_BN_FUSED_FINAL is."""
+    if act == ACT_NONE:
+        return "y"
+    if has_res:
+        return "bits" if _switch("PCOPS_BN_MASK_BITS") else "y"
+    return "coef" if _switch("PCOPS_BN_RECOMPUTE_MASK") else "y"
+
+
 class _BNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, res, weight, bias, rmean, rvar, nbt, batch_stats, momentum, eps, act, slope):
@@ -37,21 +60,34 @@ class _BNAct(torch.autograd.Function):
         y = torch.empty_like(x)  # channels_last strides preserved
         smean = torch.empty(C, dtype=torch.float32, device=x.device)
         sinv = torch.empty(C, dtype=torch.float32, device=x.device)
+        src = _mask_source(act, res is not None)
+        coef = mask = None
         with torch.cuda.device(x.device):
             nbytes = lib().pcops_batchnorm_workspace_bytes(rows, C)
             ws = Workspace.get(x.device, nbytes)
-            call("batchnorm_fwd", lib().pcops_batchnorm_fwd, ptr(x), _DT[x.dtype], ptr(res),
-                 _DT[res.dtype] if res is not None else 0, rows, C, ptr(weight), ptr(bias), ptr(rmean), ptr(rvar),
-                 float(momentum), float(eps), int(batch_stats), act, float(slope), ptr(y), ptr(smean), ptr(sinv),
-                 ptr(ws), nbytes, ptr(nbt), stream_of(x))
-        ctx.save_for_backward(x, y if act != ACT_NONE else None, weight, smean, sinv)
-        ctx.cfg = (batch_stats, act, slope, res is not None)
+            if src == "y":
+                call("batchnorm_fwd", lib().pcops_batchnorm_fwd, ptr(x), _DT[x.dtype], ptr(res),
+                     _DT[res.dtype] if res is not None else 0, rows, C, ptr(weight), ptr(bias), ptr(rmean),
+                     ptr(rvar), float(momentum), float(eps), int(batch_stats), act, float(slope), ptr(y), ptr(smean),
+                     ptr(sinv), ptr(ws), nbytes, ptr(nbt), stream_of(x))
+            else:
+                # the (scale, shift) rows and the mask outlive the call: tensors of their own, not the arena
+                coef = torch.empty(2 * C, dtype=torch.float32, device=x.device)
+                if src == "bits":
+                    mask = torch.empty(rows * C // 8, dtype=torch.uint8, device=x.device)
+                call("batchnorm_fwd_save", lib().pcops_batchnorm_fwd_save, ptr(x), _DT[x.dtype], ptr(res),
+                     _DT[res.dtype] if res is not None else 0, rows, C, ptr(weight), ptr(bias), ptr(rmean),
+                     ptr(rvar), float(momentum), float(eps), int(batch_stats), act, float(slope), ptr(y), ptr(smean),
+                     ptr(sinv), ptr(coef), ptr(mask), ptr(ws), nbytes, ptr(nbt), stream_of(x))
+        ctx.save_for_backward(x, y if act != ACT_NONE and src == "y" else None, weight, smean, sinv,
+                              coef if src == "coef" else None, mask)
+        ctx.cfg = (batch_stats, act, slope, res is not None, src)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        x, y, weight, smean, sinv = ctx.saved_tensors
-        batch_stats, act, slope, has_res = ctx.cfg
+        x, y, weight, smean, sinv, coef, mask = ctx.saved_tensors
+        batch_stats, act, slope, has_res, src = ctx.cfg
         rows, C = _rows_c(x)
         gy = gy.to(x.dtype).contiguous(memory_format=torch.channels_last)
         dx = torch.empty_like(x)
@@ -62,9 +98,14 @@ class _BNAct(torch.autograd.Function):
         with torch.cuda.device(x.device):
             nbytes = lib().pcops_batchnorm_workspace_bytes(rows, C)
             ws = Workspace.get(x.device, nbytes)
-            call("batchnorm_bwd", lib().pcops_batchnorm_bwd, ptr(gy), ptr(y), ptr(x), _DT[x.dtype], rows, C,
-                 ptr(weight), ptr(smean), ptr(sinv), int(batch_stats), act, float(slope), ptr(dx), ptr(dres),
-                 ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, stream_of(x))
+            if src == "y":
+                call("batchnorm_bwd", lib().pcops_batchnorm_bwd, ptr(gy), ptr(y), ptr(x), _DT[x.dtype], rows, C,
+                     ptr(weight), ptr(smean), ptr(sinv), int(batch_stats), act, float(slope), ptr(dx), ptr(dres),
+                     ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, stream_of(x))
+            else:
+                call("batchnorm_bwd_saved", lib().pcops_batchnorm_bwd_saved, ptr(gy), ptr(coef), ptr(mask), ptr(x),
+                     _DT[x.dtype], rows, C, ptr(weight), ptr(smean), ptr(sinv), int(batch_stats), act, float(slope),
+                     ptr(dx), ptr(dres), ptr(dgamma), ptr(dbeta), ptr(ws), nbytes, stream_of(x))
         return dx, dres, dgamma, dbeta, None, None, None, None, None, None, None, None
 
 

@@ -15,6 +15,9 @@
 // Backward:            reduce pass -> per chunk sum g, sum g * (x - mean),  g = act'(dy, y)
 //                      final       -> dgamma, dbeta, dx = a g + b x + c per channel
 //                      apply pass  -> dx (and g itself: the residual branch's gradient)
+// Neither backward pass has to read y for the activation's decision (pcops_batchnorm_fwd_save /
+// pcops_batchnorm_bwd_saved): without a residual it is recomputed from x and the forward's
+// (scale, shift), with one the forward's apply pass leaves it as one bit per element.
 // torch runs the same BasicBlock as MIOpen mean/variance + norm + clamp + add
 // forward and threshold_backward + dscale/dbias + dx (+ autograd's adds)
 // backward: 3 and 4-5 launches, each a full pass over the activation.
@@ -72,6 +75,32 @@ __device__ __forceinline__ float act_bwd(float dy, float y, float slope) {
   return dy;
 }
 
+// the decision act_bwd takes on y, and act_bwd from that decision alone
+template <int ACT>
+__device__ __forceinline__ bool act_pass(float y) {
+  if constexpr (ACT == 1) return !(y <= 0.f);
+  if constexpr (ACT == 2) return y > 0.f;
+  return true;
+}
+template <int ACT>
+__device__ __forceinline__ float act_sel(float dy, bool pass, float slope) {
+  if constexpr (ACT == 1) return pass ? dy : 0.f;
+  if constexpr (ACT == 2) return pass ? dy : dy * slope;
+  return dy;
+}
+// y as the forward's apply pass stored it (no residual): the same fma, activation and rounding to
+// the storage dtype, so act_bwd on it is bitwise act_bwd on the stored tensor
+template <int DT, int ACT>
+__device__ __forceinline__ float bn_y_again(float x, float scale, float shift, float slope) {
+  const float o = act_fwd<ACT>(__builtin_fmaf(x, scale, shift), slope);
+  return DT == 1 ? (float)(__bf16)o : o;
+}
+// where the backward passes take the activation's decision from
+//   0  y, the forward output
+//   1  x and the forward's (scale, shift): y recomputed (forward without a residual)
+//   2  the forward's packed mask: bit k of byte v = act_pass(y[8 v + k])
+constexpr int kSrcY = 0, kSrcCoef = 1, kSrcBits = 2;
+
 // A/B builds override these with -D (csrc/Makefile EXTRA)
 #ifndef PCOPS_BN_CHUNKS
 #define PCOPS_BN_CHUNKS 256
@@ -115,10 +144,12 @@ void bn_shape(long long rows, int C, int &chunks, long long &rpc) {
 // per chunk: [chunk][0][c] and [chunk][1][c].
 // MODE 0 (forward statistics): s0 = sum (x - k), s1 = sum (x - k)^2, k = x[0][c]
 // MODE 1..3 (backward, ACT = MODE-1): s0 = sum g, s1 = sum g * (x - mean), g = act'(dy, y)
-template <int DT, int MODE>
+//   SRC (MODE 2, 3): y itself, y recomputed from x and fcoef = the forward's (scale, shift), or
+//   `y` pointing at the forward's packed mask
+template <int DT, int MODE, int SRC>
 __device__ __forceinline__ void bn_accum(const void *__restrict__ x, const void *__restrict__ dy,
-                                         const void *__restrict__ y, long long e, const V8 &k, float slope,
-                                         float (&s0)[8], float (&s1)[8]) {
+                                         const void *__restrict__ y, long long e, const V8 &k, const V8 &fs,
+                                         const V8 &fh, float slope, float (&s0)[8], float (&s1)[8]) {
   V8 t;
   ld8<DT>(t, x, e);
   if constexpr (MODE == 0) {
@@ -130,11 +161,17 @@ __device__ __forceinline__ void bn_accum(const void *__restrict__ x, const void 
     }
   } else {
     V8 g, o;
+    unsigned bits = 0;
     ld8<DT>(g, dy, e);
-    if constexpr (MODE != 1) ld8<DT>(o, y, e);
+    if constexpr (MODE != 1 && SRC == kSrcY) ld8<DT>(o, y, e);
+    if constexpr (MODE != 1 && SRC == kSrcBits) bits = reinterpret_cast<const unsigned char *>(y)[e >> 3];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float gg = act_bwd<MODE - 1>(g.v[j], MODE != 1 ? o.v[j] : 0.f, slope);
+      float gg = g.v[j];
+      if constexpr (MODE != 1 && SRC == kSrcY) gg = act_bwd<MODE - 1>(gg, o.v[j], slope);
+      if constexpr (MODE != 1 && SRC == kSrcCoef)
+        gg = act_bwd<MODE - 1>(gg, bn_y_again<DT, MODE - 1>(t.v[j], fs.v[j], fh.v[j], slope), slope);
+      if constexpr (MODE != 1 && SRC == kSrcBits) gg = act_sel<MODE - 1>(gg, (bits >> j) & 1u, slope);
       s0[j] += gg;
       s1[j] = __builtin_fmaf(gg, t.v[j] - k.v[j], s1[j]);
     }
@@ -203,10 +240,11 @@ __device__ __forceinline__ void bn_final_col(int c, double s0, double s1, const 
 constexpr unsigned kBnSlots = 1u << 16;
 __device__ unsigned g_bn_arrive[kBnSlots];
 
-template <int DT, int MODE, bool FUSE>
+template <int DT, int MODE, bool FUSE, int SRC>
 __global__ __launch_bounds__(64 * kBnWaves) void bn_partial_kernel(const void *__restrict__ x,
                                                                    const void *__restrict__ dy,
                                                                    const void *__restrict__ y,
+                                                                   const float *__restrict__ fcoef,
                                                                    const float *__restrict__ mean, long long rows,
                                                                    int C, int V, long long rpc, float slope,
                                                                    float *__restrict__ part, BnFin fin,
@@ -224,6 +262,12 @@ __global__ __launch_bounds__(64 * kBnWaves) void bn_partial_kernel(const void *_
 #pragma unroll
     for (int j = 0; j < 8; ++j) k.v[j] = mean[col + j];
   }
+  V8 fs, fh;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    fs.v[j] = SRC == kSrcCoef ? fcoef[col + j] : 0.f;
+    fh.v[j] = SRC == kSrcCoef ? fcoef[C + col + j] : 0.f;
+  }
   float s0[8], s1[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) s0[j] = s1[j] = 0.f;
@@ -233,9 +277,9 @@ __global__ __launch_bounds__(64 * kBnWaves) void bn_partial_kernel(const void *_
   for (; r + (kBnUnroll - 1) * step < r1; r += kBnUnroll * step) {
     const long long e = r * C + col, es = step * C;
 #pragma unroll
-    for (int u = 0; u < kBnUnroll; ++u) bn_accum<DT, MODE>(x, dy, y, e + u * es, k, slope, s0, s1);
+    for (int u = 0; u < kBnUnroll; ++u) bn_accum<DT, MODE, SRC>(x, dy, y, e + u * es, k, fs, fh, slope, s0, s1);
   }
-  for (; r < r1; r += step) bn_accum<DT, MODE>(x, dy, y, r * C + col, k, slope, s0, s1);
+  for (; r < r1; r += step) bn_accum<DT, MODE, SRC>(x, dy, y, r * C + col, k, fs, fh, slope, s0, s1);
   for (int o = V; o < 64; o <<= 1)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -371,10 +415,12 @@ __global__ void bn_eval_coef_kernel(int C, const float *__restrict__ gamma, cons
 
 // ---- elementwise passes: 4 vectors per thread, per-channel coefficients in LDS.
 // n8 < 2^31 vectors (checked on the host), vector v covers channels (v % (C/8)) * 8 ...
-template <int DT, int RT, int ACT>
+// MASK: also leave act_pass of every stored element as one bit (byte v = vector v's 8 channels)
+template <int DT, int RT, int ACT, bool MASK>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const void *__restrict__ x, const void *__restrict__ res,
                                                        const float *__restrict__ coef, int C, unsigned n8,
-                                                       float slope, void *__restrict__ y) {
+                                                       float slope, void *__restrict__ y,
+                                                       unsigned char *__restrict__ mask) {
   extern __shared__ float sc[];  // [2][C]
   for (int i = threadIdx.x; i < 2 * C; i += 256) sc[i] = coef[i];
   __syncthreads();
@@ -388,24 +434,31 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const void *__restrict__ 
     V8 t, r;
     ld8<DT>(t, x, 8LL * v);
     if constexpr (RT >= 0) ld8<RT>(r, res, 8LL * v);
+    unsigned bits = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float o = __builtin_fmaf(t.v[k], sc[c0 + k], sc[C + c0 + k]);
       // torch adds the residual to the BN output as stored (bf16-rounded for a bf16 x)
       if constexpr (RT >= 0) o = (DT == 1 ? (float)(__bf16)o : o) + r.v[k];
       t.v[k] = act_fwd<ACT>(o, slope);
+      if constexpr (MASK) bits |= (unsigned)act_pass<ACT>(DT == 1 ? (float)(__bf16)t.v[k] : t.v[k]) << k;
     }
     st8<DT>(y, 8LL * v, t);
+    if constexpr (MASK) mask[v] = (unsigned char)bits;
   }
 }
 
-template <int DT, int ACT, bool RES>
+// SRC: as in bn_partial_kernel; kSrcCoef: fcoef = the forward's (scale, shift), kSrcBits: y = the mask
+template <int DT, int ACT, bool RES, int SRC>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const void *__restrict__ dy, const void *__restrict__ y,
                                                            const void *__restrict__ x, const float *__restrict__ coef,
-                                                           int C, unsigned n8, float slope, void *__restrict__ dx,
+                                                           const float *__restrict__ fcoef, int C, unsigned n8,
+                                                           float slope, void *__restrict__ dx,
                                                            void *__restrict__ dres) {
-  extern __shared__ float sc[];  // [3][C]
+  extern __shared__ float sc[];  // [3][C], kSrcCoef: + [2][C]
   for (int i = threadIdx.x; i < 3 * C; i += 256) sc[i] = coef[i];
+  if constexpr (ACT != 0 && SRC == kSrcCoef)
+    for (int i = threadIdx.x; i < 2 * C; i += 256) sc[3 * C + i] = fcoef[i];
   __syncthreads();
   const unsigned nv = (unsigned)C >> 3;
   const unsigned base = blockIdx.x * 1024u + threadIdx.x;
@@ -415,12 +468,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const void *__restric
     if (v >= n8) break;
     const int c0 = (int)(v % nv) * 8;
     V8 g, o, t;
+    unsigned bits = 0;
     ld8<DT>(g, dy, 8LL * v);
-    if constexpr (ACT != 0) ld8<DT>(o, y, 8LL * v);
+    if constexpr (ACT != 0 && SRC == kSrcY) ld8<DT>(o, y, 8LL * v);
+    if constexpr (ACT != 0 && SRC == kSrcBits) bits = reinterpret_cast<const unsigned char *>(y)[v];
     ld8<DT>(t, x, 8LL * v);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      g.v[k] = act_bwd<ACT>(g.v[k], ACT != 0 ? o.v[k] : 0.f, slope);
+      if constexpr (ACT != 0 && SRC == kSrcY) g.v[k] = act_bwd<ACT>(g.v[k], o.v[k], slope);
+      if constexpr (ACT != 0 && SRC == kSrcCoef)
+        g.v[k] = act_bwd<ACT>(g.v[k], bn_y_again<DT, ACT>(t.v[k], sc[3 * C + c0 + k], sc[4 * C + c0 + k], slope),
+                              slope);
+      if constexpr (ACT != 0 && SRC == kSrcBits) g.v[k] = act_sel<ACT>(g.v[k], (bits >> k) & 1u, slope);
       t.v[k] = __builtin_fmaf(sc[c0 + k], g.v[k], __builtin_fmaf(sc[C + c0 + k], t.v[k], sc[2 * C + c0 + k]));
     }
     st8<DT>(dx, 8LL * v, t);
@@ -451,59 +510,88 @@ unsigned bn_arrive_slots(int n, hipStream_t s) {
 }
 
 template <int DT, bool FUSE>
-void launch_partial_t(int mode, const void *x, const void *dy, const void *y, const float *mean, long long rows, int C,
-                      float slope, float *part, int chunks, long long rpc, const BnFin &fin, hipStream_t s) {
+void launch_partial_t(int mode, int src, const void *x, const void *dy, const void *y, const float *fcoef,
+                      const float *mean, long long rows, int C, float slope, float *part, int chunks, long long rpc,
+                      const BnFin &fin, hipStream_t s) {
   const int V = bn_v(C);
   const dim3 grid(chunks, C / 8 / V), block(64 * kBnWaves);
   const size_t lds = FUSE ? (size_t)2 * 16 * V * 8 * sizeof(double) : (size_t)kBnWaves * 2 * V * 8 * sizeof(float);
   const unsigned slot = FUSE ? bn_arrive_slots(C / 8 / V, s) : 0u;
-  switch (mode) {
-    case 0: hipLaunchKernelGGL((bn_partial_kernel<DT, 0, FUSE>), grid, block, lds, s, x, dy, y, mean, rows, C, V, rpc, slope, part, fin, slot); break;
-    case 1: hipLaunchKernelGGL((bn_partial_kernel<DT, 1, FUSE>), grid, block, lds, s, x, dy, y, mean, rows, C, V, rpc, slope, part, fin, slot); break;
-    case 2: hipLaunchKernelGGL((bn_partial_kernel<DT, 2, FUSE>), grid, block, lds, s, x, dy, y, mean, rows, C, V, rpc, slope, part, fin, slot); break;
-    default: hipLaunchKernelGGL((bn_partial_kernel<DT, 3, FUSE>), grid, block, lds, s, x, dy, y, mean, rows, C, V, rpc, slope, part, fin, slot); break;
-  }
+#define PC_BN_PARTIAL(MODE, SRC)                                                                                   \
+  hipLaunchKernelGGL((bn_partial_kernel<DT, MODE, FUSE, SRC>), grid, block, lds, s, x, dy, y, fcoef, mean, rows, C, V, \
+                     rpc, slope, part, fin, slot)
+  if (mode == 0) PC_BN_PARTIAL(0, kSrcY);
+  else if (mode == 1) PC_BN_PARTIAL(1, kSrcY);
+  else if (mode == 2 && src == kSrcY) PC_BN_PARTIAL(2, kSrcY);
+  else if (mode == 2 && src == kSrcCoef) PC_BN_PARTIAL(2, kSrcCoef);
+  else if (mode == 2) PC_BN_PARTIAL(2, kSrcBits);
+  else if (src == kSrcY) PC_BN_PARTIAL(3, kSrcY);
+  else if (src == kSrcCoef) PC_BN_PARTIAL(3, kSrcCoef);
+  else PC_BN_PARTIAL(3, kSrcBits);
+#undef PC_BN_PARTIAL
 }
 
 // partial sums + final: one launch (fused) or two
 template <int DT>
-void launch_stats(int mode, const void *x, const void *dy, const void *y, const float *mean, long long rows, int C,
-                  float slope, float *part, int chunks, long long rpc, const BnFin &fin, hipStream_t s) {
+void launch_stats(int mode, int src, const void *x, const void *dy, const void *y, const float *fcoef,
+                  const float *mean, long long rows, int C, float slope, float *part, int chunks, long long rpc,
+                  const BnFin &fin, hipStream_t s) {
   if (bn_fuse(C)) {
-    launch_partial_t<DT, true>(mode, x, dy, y, mean, rows, C, slope, part, chunks, rpc, fin, s);
+    launch_partial_t<DT, true>(mode, src, x, dy, y, fcoef, mean, rows, C, slope, part, chunks, rpc, fin, s);
     return;
   }
-  launch_partial_t<DT, false>(mode, x, dy, y, mean, rows, C, slope, part, chunks, rpc, fin, s);
+  launch_partial_t<DT, false>(mode, src, x, dy, y, fcoef, mean, rows, C, slope, part, chunks, rpc, fin, s);
   if (mode == 0)
     hipLaunchKernelGGL((bn_final_kernel<0, DT>), dim3((C + 31) / 32), dim3(512), 0, s, part, chunks, fin);
   else
     hipLaunchKernelGGL((bn_final_kernel<1, DT>), dim3((C + 31) / 32), dim3(512), 0, s, part, chunks, fin);
 }
 
-template <int DT, int RT>
-void launch_apply(int act, const void *x, const void *res, const float *coef, int C, unsigned n8, float slope, void *y,
-                  hipStream_t s) {
+template <int DT, int RT, int ACT>
+void launch_apply_a(const void *x, const void *res, const float *coef, int C, unsigned n8, float slope, void *y,
+                    unsigned char *mask, hipStream_t s) {
   const dim3 grid((n8 + 1023) / 1024);
   const size_t lds = 2 * C * sizeof(float);
-  if (act == 1)
-    hipLaunchKernelGGL((bn_apply_kernel<DT, RT, 1>), grid, dim3(256), lds, s, x, res, coef, C, n8, slope, y);
-  else if (act == 2)
-    hipLaunchKernelGGL((bn_apply_kernel<DT, RT, 2>), grid, dim3(256), lds, s, x, res, coef, C, n8, slope, y);
+  if (ACT != 0 && mask)
+    hipLaunchKernelGGL((bn_apply_kernel<DT, RT, (ACT != 0 ? ACT : 1), true>), grid, dim3(256), lds, s, x, res, coef,
+                       C, n8, slope, y, mask);
   else
-    hipLaunchKernelGGL((bn_apply_kernel<DT, RT, 0>), grid, dim3(256), lds, s, x, res, coef, C, n8, slope, y);
+    hipLaunchKernelGGL((bn_apply_kernel<DT, RT, ACT, false>), grid, dim3(256), lds, s, x, res, coef, C, n8, slope, y,
+                       mask);
+}
+
+template <int DT, int RT>
+void launch_apply(int act, const void *x, const void *res, const float *coef, int C, unsigned n8, float slope, void *y,
+                  unsigned char *mask, hipStream_t s) {
+  if (act == 1) launch_apply_a<DT, RT, 1>(x, res, coef, C, n8, slope, y, mask, s);
+  else if (act == 2) launch_apply_a<DT, RT, 2>(x, res, coef, C, n8, slope, y, mask, s);
+  else launch_apply_a<DT, RT, 0>(x, res, coef, C, n8, slope, y, nullptr, s);
+}
+
+template <int DT, int ACT, int SRC>
+void launch_bwd_apply_s(bool res, const void *dy, const void *y, const void *x, const float *coef, const float *fcoef,
+                        int C, unsigned n8, float slope, void *dx, void *dres, hipStream_t s) {
+  const dim3 grid((n8 + 1023) / 1024);
+  const size_t lds = (SRC == kSrcCoef ? 5 : 3) * C * sizeof(float);
+  if (res)
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<DT, ACT, true, SRC>), grid, dim3(256), lds, s, dy, y, x, coef, fcoef, C,
+                       n8, slope, dx, dres);
+  else
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<DT, ACT, false, SRC>), grid, dim3(256), lds, s, dy, y, x, coef, fcoef, C,
+                       n8, slope, dx, dres);
 }
 
 template <int DT, int ACT>
-void launch_bwd_apply(bool res, const void *dy, const void *y, const void *x, const float *coef, int C, unsigned n8,
-                      float slope, void *dx, void *dres, hipStream_t s) {
-  const dim3 grid((n8 + 1023) / 1024);
-  const size_t lds = 3 * C * sizeof(float);
-  if (res)
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<DT, ACT, true>), grid, dim3(256), lds, s, dy, y, x, coef, C, n8, slope,
-                       dx, dres);
-  else
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<DT, ACT, false>), grid, dim3(256), lds, s, dy, y, x, coef, C, n8, slope,
-                       dx, dres);
+void launch_bwd_apply(int src, bool res, const void *dy, const void *y, const void *x, const float *coef,
+                      const float *fcoef, int C, unsigned n8, float slope, void *dx, void *dres, hipStream_t s) {
+  if constexpr (ACT == 0) {
+    launch_bwd_apply_s<DT, ACT, kSrcY>(res, dy, y, x, coef, fcoef, C, n8, slope, dx, dres, s);
+  } else {
+    if (src == kSrcY) launch_bwd_apply_s<DT, ACT, kSrcY>(res, dy, y, x, coef, fcoef, C, n8, slope, dx, dres, s);
+    else if (src == kSrcCoef)
+      launch_bwd_apply_s<DT, ACT, kSrcCoef>(res, dy, y, x, coef, fcoef, C, n8, slope, dx, dres, s);
+    else launch_bwd_apply_s<DT, ACT, kSrcBits>(res, dy, y, x, coef, fcoef, C, n8, slope, dx, dres, s);
+  }
 }
 
 bool bn_shape_ok(long long rows, int C) {
@@ -520,12 +608,14 @@ extern "C" unsigned long long pcops_batchnorm_workspace_bytes(long long rows, in
   return ((unsigned long long)chunks * 2 * C + 3ULL * C) * sizeof(float);
 }
 
-extern "C" int pcops_batchnorm_fwd(const void *x, int dtype, const void *res, int res_dtype, long long rows, int C,
-                                   const float *gamma, const float *beta, float *running_mean, float *running_var,
-                                   float momentum, float eps, int batch_stats, int act, float slope, void *y,
-                                   float *save_mean, float *save_invstd, void *workspace,
-                                   unsigned long long workspace_bytes, long long *num_batches_tracked,
-                                   pcops_stream_t stream) {
+namespace {
+
+// coef_out: where the (scale, shift) rows go (the workspace's own slot when NULL); mask: optional
+int bn_fwd(const void *x, int dtype, const void *res, int res_dtype, long long rows, int C, const float *gamma,
+           const float *beta, float *running_mean, float *running_var, float momentum, float eps, int batch_stats,
+           int act, float slope, void *y, float *save_mean, float *save_invstd, float *coef_out, unsigned char *mask,
+           void *workspace, unsigned long long workspace_bytes, long long *num_batches_tracked,
+           pcops_stream_t stream) {
   if (rows < 0 || C <= 0 || (dtype != 0 && dtype != 1) || act < 0 || act > 2) return PCOPS_ERR_INVALID;
   if (res && res_dtype != 0 && res_dtype != 1) return PCOPS_ERR_INVALID;
   if (rows == 0) return PCOPS_OK;
@@ -539,15 +629,15 @@ extern "C" int pcops_batchnorm_fwd(const void *x, int dtype, const void *res, in
   long long rpc;
   bn_shape(rows, C, chunks, rpc);
   float *part = (float *)workspace;
-  float *coef = part + (long long)chunks * 2 * C;
+  float *coef = coef_out ? coef_out : part + (long long)chunks * 2 * C;
   if (batch_stats) {
     BnFin fin{x,         gamma,   beta,    running_mean, running_var, momentum,
               eps,       save_mean, save_invstd, nullptr, nullptr,     0,
               coef,      running_mean ? num_batches_tracked : nullptr, rows, C};
     if (dtype == 0)
-      launch_stats<0>(0, x, nullptr, nullptr, nullptr, rows, C, 0.f, part, chunks, rpc, fin, s);
+      launch_stats<0>(0, kSrcY, x, nullptr, nullptr, nullptr, nullptr, rows, C, 0.f, part, chunks, rpc, fin, s);
     else
-      launch_stats<1>(0, x, nullptr, nullptr, nullptr, rows, C, 0.f, part, chunks, rpc, fin, s);
+      launch_stats<1>(0, kSrcY, x, nullptr, nullptr, nullptr, nullptr, rows, C, 0.f, part, chunks, rpc, fin, s);
   } else {
     hipLaunchKernelGGL(bn_eval_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, s, C, gamma, beta, running_mean,
                        running_var, eps, save_mean, save_invstd, coef);
@@ -555,23 +645,23 @@ extern "C" int pcops_batchnorm_fwd(const void *x, int dtype, const void *res, in
   const unsigned n8 = (unsigned)(rows * C / 8);
   const int rt = res ? res_dtype : -1;
   if (dtype == 0) {
-    if (rt < 0) launch_apply<0, -1>(act, x, res, coef, C, n8, slope, y, s);
-    else if (rt == 0) launch_apply<0, 0>(act, x, res, coef, C, n8, slope, y, s);
-    else launch_apply<0, 1>(act, x, res, coef, C, n8, slope, y, s);
+    if (rt < 0) launch_apply<0, -1>(act, x, res, coef, C, n8, slope, y, mask, s);
+    else if (rt == 0) launch_apply<0, 0>(act, x, res, coef, C, n8, slope, y, mask, s);
+    else launch_apply<0, 1>(act, x, res, coef, C, n8, slope, y, mask, s);
   } else {
-    if (rt < 0) launch_apply<1, -1>(act, x, res, coef, C, n8, slope, y, s);
-    else if (rt == 0) launch_apply<1, 0>(act, x, res, coef, C, n8, slope, y, s);
-    else launch_apply<1, 1>(act, x, res, coef, C, n8, slope, y, s);
+    if (rt < 0) launch_apply<1, -1>(act, x, res, coef, C, n8, slope, y, mask, s);
+    else if (rt == 0) launch_apply<1, 0>(act, x, res, coef, C, n8, slope, y, mask, s);
+    else launch_apply<1, 1>(act, x, res, coef, C, n8, slope, y, mask, s);
   }
   PC_CHECK_LAUNCH();
   return PCOPS_OK;
 }
 
-extern "C" int pcops_batchnorm_bwd(const void *dy, const void *y, const void *x, int dtype, long long rows, int C,
-                                   const float *gamma, const float *save_mean, const float *save_invstd,
-                                   int batch_stats, int act, float slope, void *dx, void *dres, float *dgamma,
-                                   float *dbeta, void *workspace, unsigned long long workspace_bytes,
-                                   pcops_stream_t stream) {
+// src: where the activation's decision comes from (y: the tensor src names, fcoef: kSrcCoef only)
+int bn_bwd(int src, const void *dy, const void *y, const float *fcoef, const void *x, int dtype, long long rows, int C,
+           const float *gamma, const float *save_mean, const float *save_invstd, int batch_stats, int act, float slope,
+           void *dx, void *dres, float *dgamma, float *dbeta, void *workspace, unsigned long long workspace_bytes,
+           pcops_stream_t stream) {
   if (rows < 0 || C <= 0 || (dtype != 0 && dtype != 1) || act < 0 || act > 2) return PCOPS_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
   if (rows == 0) {
@@ -581,7 +671,8 @@ extern "C" int pcops_batchnorm_bwd(const void *dy, const void *y, const void *x,
     return PCOPS_OK;
   }
   if (!bn_shape_ok(rows, C)) return PCOPS_ERR_UNSUPPORTED;
-  if (!dy || !x || !dx || !save_mean || !save_invstd || (act != 0 && !y)) return PCOPS_ERR_INVALID;
+  if (!dy || !x || !dx || !save_mean || !save_invstd) return PCOPS_ERR_INVALID;
+  if (act != 0 && (src == kSrcCoef ? !fcoef : !y)) return PCOPS_ERR_INVALID;
   if (!workspace || workspace_bytes < pcops_batchnorm_workspace_bytes(rows, C)) return PCOPS_ERR_WORKSPACE;
   int chunks;
   long long rpc;
@@ -592,20 +683,67 @@ extern "C" int pcops_batchnorm_bwd(const void *dy, const void *y, const void *x,
   BnFin fin{x,       gamma,  nullptr, nullptr, nullptr, 0.f, 0.f, (float *)save_mean, (float *)save_invstd, dgamma,
             dbeta,   batch_stats ? 0 : 1, coef, nullptr, rows, C};
   if (dtype == 0)
-    launch_stats<0>(mode, x, dy, y, save_mean, rows, C, slope, part, chunks, rpc, fin, s);
+    launch_stats<0>(mode, src, x, dy, y, fcoef, save_mean, rows, C, slope, part, chunks, rpc, fin, s);
   else
-    launch_stats<1>(mode, x, dy, y, save_mean, rows, C, slope, part, chunks, rpc, fin, s);
+    launch_stats<1>(mode, src, x, dy, y, fcoef, save_mean, rows, C, slope, part, chunks, rpc, fin, s);
   const unsigned n8 = (unsigned)(rows * C / 8);
   const bool r = dres != nullptr;
   if (dtype == 0) {
-    if (act == 1) launch_bwd_apply<0, 1>(r, dy, y, x, coef, C, n8, slope, dx, dres, s);
-    else if (act == 2) launch_bwd_apply<0, 2>(r, dy, y, x, coef, C, n8, slope, dx, dres, s);
-    else launch_bwd_apply<0, 0>(r, dy, y, x, coef, C, n8, slope, dx, dres, s);
+    if (act == 1) launch_bwd_apply<0, 1>(src, r, dy, y, x, coef, fcoef, C, n8, slope, dx, dres, s);
+    else if (act == 2) launch_bwd_apply<0, 2>(src, r, dy, y, x, coef, fcoef, C, n8, slope, dx, dres, s);
+    else launch_bwd_apply<0, 0>(src, r, dy, y, x, coef, fcoef, C, n8, slope, dx, dres, s);
   } else {
-    if (act == 1) launch_bwd_apply<1, 1>(r, dy, y, x, coef, C, n8, slope, dx, dres, s);
-    else if (act == 2) launch_bwd_apply<1, 2>(r, dy, y, x, coef, C, n8, slope, dx, dres, s);
-    else launch_bwd_apply<1, 0>(r, dy, y, x, coef, C, n8, slope, dx, dres, s);
+    if (act == 1) launch_bwd_apply<1, 1>(src, r, dy, y, x, coef, fcoef, C, n8, slope, dx, dres, s);
+    else if (act == 2) launch_bwd_apply<1, 2>(src, r, dy, y, x, coef, fcoef, C, n8, slope, dx, dres, s);
+    else launch_bwd_apply<1, 0>(src, r, dy, y, x, coef, fcoef, C, n8, slope, dx, dres, s);
   }
   PC_CHECK_LAUNCH();
   return PCOPS_OK;
+}
+
+}  // namespace
+
+extern "C" int pcops_batchnorm_fwd(const void *x, int dtype, const void *res, int res_dtype, long long rows, int C,
+                                   const float *gamma, const float *beta, float *running_mean, float *running_var,
+                                   float momentum, float eps, int batch_stats, int act, float slope, void *y,
+                                   float *save_mean, float *save_invstd, void *workspace,
+                                   unsigned long long workspace_bytes, long long *num_batches_tracked,
+                                   pcops_stream_t stream) {
+  return bn_fwd(x, dtype, res, res_dtype, rows, C, gamma, beta, running_mean, running_var, momentum, eps, batch_stats,
+                act, slope, y, save_mean, save_invstd, nullptr, nullptr, workspace, workspace_bytes,
+                num_batches_tracked, stream);
+}
+
+extern "C" int pcops_batchnorm_bwd(const void *dy, const void *y, const void *x, int dtype, long long rows, int C,
+                                   const float *gamma, const float *save_mean, const float *save_invstd,
+                                   int batch_stats, int act, float slope, void *dx, void *dres, float *dgamma,
+                                   float *dbeta, void *workspace, unsigned long long workspace_bytes,
+                                   pcops_stream_t stream) {
+  return bn_bwd(kSrcY, dy, y, nullptr, x, dtype, rows, C, gamma, save_mean, save_invstd, batch_stats, act, slope, dx,
+                dres, dgamma, dbeta, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pcops_batchnorm_fwd_save(const void *x, int dtype, const void *res, int res_dtype, long long rows,
+                                        int C, const float *gamma, const float *beta, float *running_mean,
+                                        float *running_var, float momentum, float eps, int batch_stats, int act,
+                                        float slope, void *y, float *save_mean, float *save_invstd, float *save_coef,
+                                        unsigned char *save_mask, void *workspace,
+                                        unsigned long long workspace_bytes, long long *num_batches_tracked,
+                                        pcops_stream_t stream) {
+  if (!save_coef) return PCOPS_ERR_INVALID;
+  return bn_fwd(x, dtype, res, res_dtype, rows, C, gamma, beta, running_mean, running_var, momentum, eps, batch_stats,
+                act, slope, y, save_mean, save_invstd, save_coef, save_mask, workspace, workspace_bytes,
+                num_batches_tracked, stream);
+}
+
+extern "C" int pcops_batchnorm_bwd_saved(const void *dy, const float *save_coef, const unsigned char *save_mask,
+                                         const void *x, int dtype, long long rows, int C, const float *gamma,
+                                         const float *save_mean, const float *save_invstd, int batch_stats, int act,
+                                         float slope, void *dx, void *dres, float *dgamma, float *dbeta,
+                                         void *workspace, unsigned long long workspace_bytes, pcops_stream_t stream) {
+  if (save_mask)
+    return bn_bwd(kSrcBits, dy, save_mask, nullptr, x, dtype, rows, C, gamma, save_mean, save_invstd, batch_stats, act,
+                  slope, dx, dres, dgamma, dbeta, workspace, workspace_bytes, stream);
+  return bn_bwd(kSrcCoef, dy, nullptr, save_coef, x, dtype, rows, C, gamma, save_mean, save_invstd, batch_stats, act,
+                slope, dx, dres, dgamma, dbeta, workspace, workspace_bytes, stream);
 }

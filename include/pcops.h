@@ -572,6 +572,30 @@ int pcops_pcsa_backward(const void *x, int x_dtype, const void *dout, int dout_d
                         int gates_dtype, const float *basis, int patches, int K, int C, void *dx, void *dgates,
                         pcops_stream_t stream);
 
+/* ---------------- GeoSpecNet spectral pooling (models/GeoSpecNet.py:68-105) ----------------
+ * SpectralAdapter.forward between the softmax and the channel MLP, on token-major
+ * features x (B, N, C) (dtype code 0 = fp32, 1 = bf16), neighbour indices idx
+ * (B, N, K) int32, softmax weights a (B, N, K) fp32, frequency gates g (C, K) fp32
+ * and the DCT-II basis W = basis (K, K) row-major fp32:
+ *   ahat[b,n,m]   = sum_k W[k,m] a[b,n,k]
+ *   Xhat[b,n,c,m] = sum_j x[b, idx[b,n,j], c] W[j,m]
+ *   out[b,n,c]    = sum_m g[c,m] ahat[b,n,m] Xhat[b,n,c,m]          (out in x_dtype)
+ * pcops_spectral_pool_backward, for dout (B, N, C) in dout_dtype: dx (B, N, C) in
+ * x_dtype, da (B, N, K) fp32, dg (C, K) fp32; every element is stored exactly once
+ * (no fill by the caller, no atomics) and every sum runs in a fixed order, so the
+ * results are bitwise reproducible.  fp32 accumulation throughout.
+ * An index outside [0, N) is skipped in both directions (its feature counts as
+ * zero) and is never dereferenced.
+ * K in {4, 8, 16, 32}, N*K <= 16384, any C >= 1; anything else returns
+ * PCOPS_ERR_UNSUPPORTED.  workspace (backward): pcops_spectral_pool_workspace_bytes. */
+unsigned long long pcops_spectral_pool_workspace_bytes(int B, int N, int K, int C);
+int pcops_spectral_pool_forward(const void *x, int x_dtype, const int *idx, const float *a, const float *g,
+                                const float *basis, int B, int N, int K, int C, void *out, pcops_stream_t stream);
+int pcops_spectral_pool_backward(const void *x, int x_dtype, const void *dout, int dout_dtype, const int *idx,
+                                 const float *a, const float *g, const float *basis, int B, int N, int K, int C,
+                                 void *dx, float *da, float *dg, void *workspace, unsigned long long workspace_bytes,
+                                 pcops_stream_t stream);
+
 /* ---------------- depth renderers ----------------
  * PCViews.get_img (models/model_utils.py:1196-1234 -> points2depth :1080-1115 ->
  * distribute :1004-1077, size 1): points (B,N,3); rot (V,3,3) row-major =

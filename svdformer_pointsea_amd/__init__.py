@@ -9,6 +9,7 @@ Drop-in modules mirroring the reference's operator API:
   svdformer_pointsea_amd.attention        <- self/cross_attention, SDG_Decoder (model_utils.py)
   svdformer_pointsea_amd.render           <- PCViews (model_utils.py), PCViews_Real (mv_utils_zs.py)
   svdformer_pointsea_amd.svdformer        <- models/SVDFormer.py + utils/loss_utils.get_loss
+  svdformer_pointsea_amd.geospecnet       <- models/GeoSpecNet.py + the step of core/train_geospec.py
 All compute runs in libpcops.so (include/pcops.h); there is no CPU fallback.
 """
 from ._lib import LIB_PATH, lib  # noqa: F401

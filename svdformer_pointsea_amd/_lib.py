@@ -108,6 +108,9 @@ _SIGS = {
     "pcops_conv3x3_c1_wgrad": (I, [P, P, I, I, I, P, I, P, ULL, P]),
     "pcops_pcsa_forward": (I, [P, I, P, I, P, I, I, I, P, P]),
     "pcops_pcsa_backward": (I, [P, I, P, I, P, I, P, I, I, I, P, P, P]),
+    "pcops_spectral_pool_workspace_bytes": (ULL, [I, I, I, I]),
+    "pcops_spectral_pool_forward": (I, [P, I, P, P, P, P, I, I, I, I, P, P]),
+    "pcops_spectral_pool_backward": (I, [P, I, P, I, P, P, P, P, I, I, I, I, P, P, P, P, ULL, P]),
     "pcops_points2depth_workspace_bytes": (ULL, [I, I, I, I]),
     "pcops_points2depth": (I, [P, P, P, I, I, I, I, I, P, P, ULL, P]),
     "pcops_points2grid": (I, [P, P, P, P, I, I, I, I, I, P, P]),

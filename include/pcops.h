@@ -68,20 +68,26 @@ int pcops_furthest_point_sampling_counts(const float *xyz, const int *counts, in
 int pcops_crop_pack(const float *dist, const float *xyz, const long long *start, const long long *count, int B, int N,
                     int n_max, float *out, int *counts, pcops_stream_t stream);
 
+/* Index rule of gather_points, group_points, three_interpolate and their grads: an index
+ * outside [0, n) (n = N, or M for three_interpolate) is skipped -- it counts as zero: the
+ * forward reads 0 for that position, the grad adds nothing for it -- and is never
+ * dereferenced.  (The reference reads / writes out of bounds there.) */
+
 /* gather_points(points, idx): sampling.cpp:15-38, sampling_gpu.cu:8-30.
- * points (B,C,N), idx (B,M) -> out (B,C,M). */
+ * points (B,C,N), idx (B,M) -> out (B,C,M).  Out-of-range idx: see the index rule above. */
 int pcops_gather_points(const float *points, const int *idx, int B, int C, int N, int M, float *out,
                         pcops_stream_t stream);
 /* gather_points_grad(grad_out, idx, n): sampling.cpp:40-64, sampling_gpu.cu:34-57.
- * grad_out (B,C,M) -> grad_points (B,C,N) (overwritten). */
+ * grad_out (B,C,M) -> grad_points (B,C,N) (overwritten; out-of-range idx adds nothing). */
 int pcops_gather_points_grad(const float *grad_out, const int *idx, int B, int C, int N, int M, float *grad_points,
                              pcops_stream_t stream);
 
 /* group_points(points, idx): group_points.cpp:12-36, group_points_gpu.cu:8-39.
- * points (B,C,N), idx (B,S,K) -> out (B,C,S,K). */
+ * points (B,C,N), idx (B,S,K) -> out (B,C,S,K).  Out-of-range idx reads 0 (index rule above). */
 int pcops_group_points(const float *points, const int *idx, int B, int C, int N, int S, int K, float *out,
                        pcops_stream_t stream);
-/* group_points_grad(grad_out, idx, n): group_points.cpp:38-62, group_points_gpu.cu:43-75. */
+/* group_points_grad(grad_out, idx, n): group_points.cpp:38-62, group_points_gpu.cu:43-75.
+ * grad_out (B,C,S,K) -> grad_points (B,C,N) (overwritten; out-of-range idx adds nothing). */
 int pcops_group_points_grad(const float *grad_out, const int *idx, int B, int C, int N, int S, int K,
                             float *grad_points, pcops_stream_t stream);
 
@@ -133,10 +139,12 @@ int pcops_ball_query(const float *new_xyz, const float *xyz, int B, int N, int M
 int pcops_three_nn(const float *unknown, const float *known, int B, int N, int M, float *dist2, int *idx,
                    pcops_stream_t stream);
 /* three_interpolate(points, idx, weight): interpolate.cpp:40-68, interpolate_gpu.cu:72-111.
- * points (B,C,M), idx/weight (B,N,3) -> out (B,C,N). */
+ * points (B,C,M), idx/weight (B,N,3) -> out (B,C,N).  An idx outside [0, M) contributes 0
+ * (index rule above). */
 int pcops_three_interpolate(const float *points, const int *idx, const float *weight, int B, int C, int M, int N,
                             float *out, pcops_stream_t stream);
-/* three_interpolate_grad(grad_out, idx, weight, m): interpolate.cpp:69-99, interpolate_gpu.cu:116-154. */
+/* three_interpolate_grad(grad_out, idx, weight, m): interpolate.cpp:69-99, interpolate_gpu.cu:116-154.
+ * grad_out (B,C,N) -> grad_points (B,C,M) (overwritten; an idx outside [0, M) adds nothing). */
 int pcops_three_interpolate_grad(const float *grad_out, const int *idx, const float *weight, int B, int C, int N,
                                  int M, float *grad_points, pcops_stream_t stream);
 

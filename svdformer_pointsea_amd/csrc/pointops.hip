@@ -253,7 +253,7 @@ extern "C" int pcops_ball_query(const float *new_xyz, const float *xyz, int B, i
   if (B < 0 || N < 0 || M < 0 || nsample < 0) return PCOPS_ERR_INVALID;
   const size_t tot = (size_t)B * M;
   if (tot == 0 || nsample == 0) return PCOPS_OK;
-  if (!new_xyz || !xyz || !idx) return PCOPS_ERR_INVALID;
+  if (!new_xyz || (N > 0 && !xyz) || !idx) return PCOPS_ERR_INVALID;  // an empty cloud may be NULL: never read
   hipLaunchKernelGGL(ball_query_kernel, dim3(grid_for(tot, 64)), dim3(64), 0, (hipStream_t)stream, new_xyz, xyz, B, N,
                      M, radius * radius, nsample, idx);
   PC_CHECK_LAUNCH();
@@ -264,7 +264,7 @@ extern "C" int pcops_three_nn(const float *unknown, const float *known, int B, i
                               pcops_stream_t stream) {
   if (B < 0 || N < 0 || M < 0) return PCOPS_ERR_INVALID;
   if (B == 0 || N == 0) return PCOPS_OK;
-  if (!unknown || !known || !dist2 || !idx) return PCOPS_ERR_INVALID;
+  if (!unknown || (M > 0 && !known) || !dist2 || !idx) return PCOPS_ERR_INVALID;  // M == 0: known is never read
   const dim3 grid((N + 255) / 256, B);
   hipLaunchKernelGGL(three_nn_kernel, grid, dim3(256), sizeof(float4) * 1024, (hipStream_t)stream, unknown, known, B,
                      N, M, dist2, idx);
@@ -277,7 +277,7 @@ extern "C" int pcops_three_interpolate(const float *points, const int *idx, cons
   if (B < 0 || C < 0 || M < 0 || N < 0) return PCOPS_ERR_INVALID;
   const size_t total = (size_t)B * C * N;
   if (total == 0) return PCOPS_OK;
-  if (!points || !idx || !weight || !out) return PCOPS_ERR_INVALID;
+  if ((M > 0 && !points) || !idx || !weight || !out) return PCOPS_ERR_INVALID;  // M == 0: every idx is out of range
   hipLaunchKernelGGL(three_interp_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, points, idx,
                      weight, C, M, N, total, out);
   PC_CHECK_LAUNCH();

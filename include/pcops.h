@@ -604,6 +604,34 @@ int pcops_spectral_pool_backward(const void *x, int x_dtype, const void *dout, i
                                  void *dx, float *da, float *dg, void *workspace, unsigned long long workspace_bytes,
                                  pcops_stream_t stream);
 
+/* ---------------- point-MLP max (core/train_55.py:21-46, SimplePointDiscriminator) ----------------
+ * The shared per-point MLP 3 -> H -> H -> H of the ShapeNet-55 discriminator and the max
+ * over the N points, in one pass: x (B, N, 3) fp32; w1 (H, 3), w2 and w3 (H, H) row-major
+ * [out][in] (the Conv1d weights without the trailing 1); b1, b2, b3 (H).
+ *   f[b,n,:] = W3 act(W2 act(W1 x[b,n] + b1) + b2) + b3,  act(v) = v > 0 ? v : slope v
+ *   out[b,c] = max_n f[b,n,c]   (B, H) fp32;  arg[b,c] = the lowest n attaining it (B, H) int32
+ * A NaN in f[b,.,c] wins as in torch.max: out is NaN, arg the first NaN's index.
+ * fp32 operands and accumulation; every dot product runs in one fixed k order, so a
+ * point's f has the same bits wherever it sits in the cloud.  The N axis is split into
+ * tiles of PCOPS_POINT_MLP_TILE points per workgroup; the tiles' (max, arg) pairs go
+ * through the workspace (arbitrary on entry) and are finished in a second launch.  Every
+ * element of out and arg is stored exactly once, nothing is filled by the caller or the
+ * library, and the results are bitwise reproducible.
+ * B or N <= 0: PCOPS_ERR_INVALID.  H other than 64 or 128: PCOPS_ERR_UNSUPPORTED.
+ * workspace NULL or below pcops_point_mlp_max_workspace_bytes: PCOPS_ERR_WORKSPACE, nothing
+ * is launched.
+ * pcops_point_mlp_max_scatter, the deterministic accumulate of the sparse backward:
+ * dx[b,n,:] = sum over c (ascending) with arg[b,c] == n of dxw[b,c,:], for dxw (B, H, 3),
+ * dx (B, N, 3); every element of dx is stored once (zero where no channel won). */
+#define PCOPS_POINT_MLP_TILE 256
+unsigned long long pcops_point_mlp_max_workspace_bytes(int B, int N, int H);
+int pcops_point_mlp_max_forward(const float *x, const float *w1, const float *b1, const float *w2, const float *b2,
+                                const float *w3, const float *b3, float slope, int B, int N, int H, float *out,
+                                int *arg, void *workspace, unsigned long long workspace_bytes,
+                                pcops_stream_t stream);
+int pcops_point_mlp_max_scatter(const float *dxw, const int *arg, int B, int N, int H, float *dx,
+                                pcops_stream_t stream);
+
 /* ---------------- depth renderers ----------------
  * PCViews.get_img (models/model_utils.py:1196-1234 -> points2depth :1080-1115 ->
  * distribute :1004-1077, size 1): points (B,N,3); rot (V,3,3) row-major =

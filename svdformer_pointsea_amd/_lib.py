@@ -111,6 +111,9 @@ _SIGS = {
     "pcops_spectral_pool_workspace_bytes": (ULL, [I, I, I, I]),
     "pcops_spectral_pool_forward": (I, [P, I, P, P, P, P, I, I, I, I, P, P]),
     "pcops_spectral_pool_backward": (I, [P, I, P, I, P, P, P, P, I, I, I, I, P, P, P, P, ULL, P]),
+    "pcops_point_mlp_max_workspace_bytes": (ULL, [I, I, I]),
+    "pcops_point_mlp_max_forward": (I, [P, P, P, P, P, P, P, F, I, I, I, P, P, P, ULL, P]),
+    "pcops_point_mlp_max_scatter": (I, [P, P, I, I, I, P, P]),
     "pcops_points2depth_workspace_bytes": (ULL, [I, I, I, I]),
     "pcops_points2depth": (I, [P, P, P, I, I, I, I, I, P, P, ULL, P]),
     "pcops_points2grid": (I, [P, P, P, P, I, I, I, I, I, P, P]),

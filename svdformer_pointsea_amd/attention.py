@@ -1080,15 +1080,12 @@ _FUSED_SIDE = os.environ.get("PCOPS_FUSED_SIDE", "0") == "1"          # diagnost
 _GELU_SUM = os.environ.get("PCOPS_GELU_SUM", "1") == "1"
 _PCOPS_BLEND = os.environ.get("PCOPS_BLEND", "1") != "0"   # A/B switch: PointSea path selection in one launch
 # in_proj bias sums inside the attention backward passes (A/B switch)
-# the in-pass bias sums exist only in the v2/v3 bf16 kernels: the PCOPS_ATTN_V1 A/B
-# switch (libpcops returns UNSUPPORTED for *_colsum there) takes the plain passes
 # bf16, head_dim >= 96: the one-call backward with dQ read back from the dS the dK/dV pass
 # stores (opt-in, PCOPS_ATTN_FUSED=1): measured no faster than recomputing S / dP -- at
 # 2048^2 hd 128 the dS^T stores add 0.38 ms to the dK/dV pass and the dQ read-back takes
 # 0.57 ms, against the 0.91 ms dQ pass it replaces (profiles/r4_attn_ds_ab.txt)
 _ATTN_FUSED = os.environ.get("PCOPS_ATTN_FUSED", "0") == "1"
-_ATTN_COLSUM = (os.environ.get("PCOPS_ATTN_COLSUM", "1") != "0"
-                and os.environ.get("PCOPS_ATTN_V1", "0") != "1")
+_ATTN_COLSUM = os.environ.get("PCOPS_ATTN_COLSUM", "1") != "0"
 _DEBUG_CONTIG = os.environ.get("PCOPS_DEBUG_CONTIG", "0") == "1"   # diagnostic: report _Linear operand copies
 _STRIDED_G = os.environ.get("PCOPS_STRIDED_G", "1") != "0"           # A/B switch: row-strided output gradients in place
 

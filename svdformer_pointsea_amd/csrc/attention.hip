@@ -16,8 +16,7 @@
 // Precision: bf16 operands (v_mfma_f32_32x32x16_bf16, fp32 accumulate) for
 // speed, or fp32 operands (v_mfma_f32_32x32x2_f32, exact fp32 fma chain) for
 // the parity build.
-#include <cstdlib>
-
+#include <initializer_list>
 #include <type_traits>
 
 #include "common.h"
@@ -43,61 +42,10 @@ __device__ __forceinline__ int acc_row(int r, int h) { return (r & 3) + 8 * (r >
 __device__ __forceinline__ float other_half(float v) { return __shfl_xor(v, 32, 64); }
 
 // ----------------------------------------------------------------- precisions
+// The first-generation kernels (attn_fwd / attn_dq / attn_dkv_kernel<T, D>) are the exact fp32
+// path: fp32 is their only precision.  bf16 runs the v2 / v3 kernels further down.
 template <typename T, int D>
 struct Prec;
-
-template <int D>
-struct Prec<__bf16, D> {
-  static constexpr int kStride = D + 8;  // LDS row stride (elements): 16-B shift per row
-  struct Frag {
-    bf16x8 v[D / 16];
-  };
-  // entity fragment: lane l holds entity l&31, d = 16s + 8h + j
-  __device__ static void load_frag(Frag &f, const __bf16 *row, bool valid) {
-    const int h = lane_() >> 5;
-#pragma unroll
-    for (int s = 0; s < D / 16; ++s) {
-      if (valid)
-        f.v[s] = *reinterpret_cast<const bf16x8 *>(row + 16 * s + 8 * h);
-      else
-        f.v[s] = bf16x8{};
-    }
-  }
-  __device__ static void product1(f32x16 &acc, const __bf16 *lds, const Frag &f) {
-    const int l = lane_(), h = l >> 5;
-    const __bf16 *rp = lds + (l & 31) * kStride + 8 * h;
-#pragma unroll
-    for (int s = 0; s < D / 16; ++s) {
-      const bf16x8 a = *reinterpret_cast<const bf16x8 *>(rp + 16 * s);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, f.v[s], acc, 0, 0, 0);
-    }
-  }
-  // Y[db] += Rows^T . X   (X fp32 accumulator, converted to bf16 in place)
-  __device__ static void product2(f32x16 (&Y)[D / 32], const __bf16 *lds, const f32x16 &X) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const int l = lane_(), h = l >> 5, g = (l >> 4) & 1, i = l & 15, q = i >> 2, p = i & 3;
-    typedef __attribute__((address_space(3))) short4v lds_s4;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      bf16x8 b;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) b[e] = (__bf16)X[8 * s + e];
-      const int row0 = 16 * s + 4 * h + q;
-#pragma unroll
-      for (int db = 0; db < D / 32; ++db) {
-        const int col = db * 32 + 16 * g + 4 * p;
-        const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4 *)(lds + row0 * kStride + col));
-        const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4 *)(lds + (row0 + 8) * kStride + col));
-        const bf16x8 a = __builtin_shufflevector(__builtin_bit_cast(bf16x4, lo), __builtin_bit_cast(bf16x4, hi), 0, 1,
-                                                 2, 3, 4, 5, 6, 7);
-        Y[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, Y[db], 0, 0, 0);
-      }
-    }
-#endif
-  }
-  __device__ static float to_f(__bf16 v) { return (float)v; }
-  __device__ static __bf16 from_f(float v) { return (__bf16)v; }
-};
 
 template <int D>
 struct Prec<float, D> {
@@ -127,34 +75,22 @@ struct Prec<float, D> {
         Y[db] = __builtin_amdgcn_mfma_f32_32x32x2f32(rp[db * 32], X[r], Y[db], 0, 0, 0);
     }
   }
-  __device__ static float to_f(float v) { return v; }
-  __device__ static float from_f(float v) { return v; }
 };
 
 // stage rows [r0, r0+32) x D of a (bh-offset) tensor into LDS; rows >= L -> 0
 template <typename T, int D>
 __device__ __forceinline__ void stage_tile(T *lds, const T *base, long long s_row, int r0, int L) {
   constexpr int kStride = Prec<T, D>::kStride;
-  if constexpr (sizeof(T) == 2) {
-    constexpr int kChunks = D / 8;  // 16-byte chunks per row
-    for (int c = threadIdx.x; c < kRows * kChunks; c += kThreads) {
-      const int row = c / kChunks, ch = c - row * kChunks;
-      bf16x8 v{};
-      if (r0 + row < L) v = *reinterpret_cast<const bf16x8 *>(base + (long long)(r0 + row) * s_row + ch * 8);
-      *reinterpret_cast<bf16x8 *>(lds + row * kStride + ch * 8) = v;
-    }
-  } else {
-    constexpr int kChunks = D / 4;
-    for (int c = threadIdx.x; c < kRows * kChunks; c += kThreads) {
-      const int row = c / kChunks, ch = c - row * kChunks;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r0 + row < L) v = *reinterpret_cast<const float4 *>(base + (long long)(r0 + row) * s_row + ch * 4);
-      T *dst = lds + row * kStride + ch * 4;
-      dst[0] = v.x;
-      dst[1] = v.y;
-      dst[2] = v.z;
-      dst[3] = v.w;
-    }
+  constexpr int kChunks = D / 4;
+  for (int c = threadIdx.x; c < kRows * kChunks; c += kThreads) {
+    const int row = c / kChunks, ch = c - row * kChunks;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r0 + row < L) v = *reinterpret_cast<const float4 *>(base + (long long)(r0 + row) * s_row + ch * 4);
+    T *dst = lds + row * kStride + ch * 4;
+    dst[0] = v.x;
+    dst[1] = v.y;
+    dst[2] = v.z;
+    dst[3] = v.w;
   }
 }
 
@@ -333,7 +269,7 @@ __global__ void attn_delta_kernel(const T *__restrict__ O, const T *__restrict__
   const T *o = O + st.o_off(bh) + (long long)q * st.o_srow;
   const T *g = dO + st.o_off(bh) + (long long)q * st.o_srow;
   float s = 0.f;
-  for (int d = lane_(); d < D; d += 64) s += Prec<T, 32>::to_f(o[d]) * Prec<T, 32>::to_f(g[d]);
+  for (int d = lane_(); d < D; d += 64) s += (float)o[d] * (float)g[d];
   s = wave_sum_f32(s);
   if (lane_() == 0) delta[row] = s;
 }
@@ -448,9 +384,6 @@ constexpr int kKT = 64;  // keys per tile
 #define PCOPS_SCHED_DS 1
 #endif
 constexpr bool kSchedDs = PCOPS_SCHED_DS;  // 0: compiler's own LDS/MFMA order (A/B builds)
-#ifndef PCOPS_DQ_A
-#define PCOPS_DQ_A 2  // dQ pass (two-half form): LDS reads issued this many MFMAs ahead; 0 = plain chains (A/B)
-#endif
 #ifndef PCOPS_DEFER_LOG2
 #define PCOPS_DEFER_LOG2 8.f  // 0 = rescale on every max increase (A/B builds)
 #endif
@@ -790,45 +723,60 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC))) 
   if (h == 0 && qi < Lq && lse) lse[(long long)bh * Lq + qi] = (m + log2f(lsum)) * kLn2;
 }
 
-int env_int(const char *name, int dflt) {
-  const char *e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
+// ----------------------------------------------------------------- host launch path
+// per-block column partial sums of the gradients a backward launch stores (the
+// *_colsum entry points): dQ in `a`; dK in `a`, dV in `b`; row (bh * nrb + rb) of
+// D floats each, nrb = the launch's row blocks per (batch, head), set by the launcher
+struct ColPart {
+  float *a = nullptr, *b = nullptr;
+  int nrb = 0;
+};
 
-template <int D, int NW, int OCC>
-int launch_fwd2_occ(const void *q, const void *k, const void *v, void *o, float *lse, int BH, int Lq, int Lk,
-                    float scale, const Strides &st, hipStream_t s) {
-  using C = Fwd2Cfg<D, NW>;
-  static const hipError_t attr = hipFuncSetAttribute((const void *)attn_fwd2_kernel<D, NW, OCC>,
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::kLds);
+// What the host passes from an entry point down to a launch: built once per call, handed on by
+// const reference (the kernels take scalars).  A pass reads the fields it needs; the rest stay null.
+struct AttnArgs {
+  const void *q, *k, *v;
+  int BH, Lq, Lk;
+  float scale;
+  Strides st;
+  hipStream_t s;
+  void *out = nullptr;         // forward: O (written) ...
+  float *lse_out = nullptr;    // ... and the row log-sum-exp (optional)
+  const void *o = nullptr;     // backward: the forward's O -- non-null selects the fused delta (written to delta_out)
+  const void *dout = nullptr;  // addressed with the o strides; dq / dk / dv with the q / k / v strides
+  const float *lse = nullptr, *delta = nullptr;
+  float *delta_out = nullptr;
+  void *dq = nullptr, *dk = nullptr, *dv = nullptr;
+  ColPart *cp = nullptr;       // non-null: the launch also forms column partial sums (and sets cp->nrb)
+};
+
+// Launch Kernel with `lds` bytes of dynamic LDS.  More than 64 KB needs the attribute set first:
+// once per kernel (the static is per instantiation of this template, i.e. per Kernel).
+template <auto Kernel, typename... KArgs>
+int launch_lds(dim3 grid, int threads, size_t lds, hipStream_t s, const KArgs &...kargs) {
+  static const hipError_t attr =
+      hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (attr != hipSuccess) return PCOPS_ERR_LAUNCH;
-  const dim3 grid((Lq + NW * 32 - 1) / (NW * 32), BH);
-  hipLaunchKernelGGL((attn_fwd2_kernel<D, NW, OCC>), grid, dim3(C::kThr), C::kLds, s, (const __bf16 *)q,
-                     (const __bf16 *)k, (const __bf16 *)v, (__bf16 *)o, lse, Lq, Lk, scale, st);
+  hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, s, kargs...);
   PC_CHECK_LAUNCH();
   return PCOPS_OK;
 }
 
-// Occupancy: 8-wave blocks at <= 128 VGPRs run 2 blocks per CU instead of
-// one (130 -> 128 for D = 64: 0.466 -> 0.379 ms at (2048, 2048, B*H = 256)).
-// D = 128 needs ~200 (Y alone is 64).  PCOPS_FWD_OCC=1 lifts the cap (A/B).
-// 4-wave blocks (short sequences) are capped at 2 waves per SIMD: left
-// alone the compiler gives them 400+ registers (one wave per SIMD).
+// Forward blocks: 8 waves at Lq > 128, 4 below (fwd2_dispatch).  Occupancy: 8-wave blocks at
+// <= 128 VGPRs run 2 blocks per CU instead of one (130 -> 128 for D = 64: 0.466 -> 0.379 ms at
+// (2048, 2048, B*H = 256)), so D <= 64 is capped there; D = 128 needs ~200 (Y alone is 64).
+// 4-wave blocks (short sequences) are capped at 2 waves per SIMD: left alone the compiler
+// gives them 400+ registers (one wave per SIMD).  D = 96 runs 4-wave blocks at any length
+// (201 VGPRs: two independent blocks per CU beat one 8-wave block at 185, 512^2 0.052 ->
+// 0.047 ms); D = 128 does not (2048^2 0.644 -> 0.719 ms).
 template <int D, int NW>
-int launch_fwd2(const void *q, const void *k, const void *v, void *o, float *lse, int BH, int Lq, int Lk, float scale,
-                const Strides &st, hipStream_t s) {
-  static const int occ = env_int("PCOPS_FWD_OCC", 4);
-  if constexpr (D <= 64 && NW == 8) {
-    if (occ == 4) return launch_fwd2_occ<D, NW, 4>(q, k, v, o, lse, BH, Lq, Lk, scale, st, s);
-  }
-  // D = 96 runs 4-wave blocks at any length (201 VGPRs: two independent
-  // blocks per CU beat one 8-wave block at 185, 512^2 0.052 -> 0.047 ms);
-  // D = 128 does not (2048^2 0.644 -> 0.719 ms)
-  if constexpr (NW == 4 || D == 96) {
-    return launch_fwd2_occ<D, 4, 2>(q, k, v, o, lse, BH, Lq, Lk, scale, st, s);
-  } else {
-    return launch_fwd2_occ<D, NW, 1>(q, k, v, o, lse, BH, Lq, Lk, scale, st, s);
-  }
+int launch_fwd2(const AttnArgs &a) {
+  constexpr int OCC = (D <= 64 && NW == 8) ? 4 : NW == 4 ? 2 : 1;
+  using C = Fwd2Cfg<D, NW>;
+  const dim3 grid((a.Lq + NW * 32 - 1) / (NW * 32), a.BH);
+  return launch_lds<attn_fwd2_kernel<D, NW, OCC>>(grid, C::kThr, C::kLds, a.s, (const __bf16 *)a.q,
+                                                  (const __bf16 *)a.k, (const __bf16 *)a.v, (__bf16 *)a.out,
+                                                  a.lse_out, a.Lq, a.Lk, a.scale, a.st);
 }
 
 // ----------------------------------------------------------------- backward, bf16 (v2)
@@ -920,21 +868,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OC
       }
     } else {
       f32x16 S0 = f32x16{}, S1 = f32x16{}, G0 = f32x16{}, G1 = f32x16{};
-#if PCOPS_DQ_A > 0
-      // the two key halves' chains interleaved, each LDS read issued PCOPS_DQ_A MFMAs ahead
-      // (the plain chains waited lgkmcnt(0) before every MFMA: the read latency exposed 32 times
-      // a tile); per accumulator the MFMA order is k_product's, so dQ is bitwise unchanged
+      // the two key halves' chains interleaved, each LDS read issued two MFMAs ahead (the plain
+      // chains waited lgkmcnt(0) before every MFMA, the read latency exposed 32 times a tile:
+      // hd 128 dq 0.842-0.855 -> 0.817-0.832 ms, three ahead measured the same,
+      // profiles/r6_attn_dq_readahead_ab.txt); per accumulator the MFMA order is k_product's
       k_product2<D>(S0, ck, qf, S1, ck + 32 * C::kKS, qf);
-      sched_ds_mfma<D / 8, 1, PCOPS_DQ_A>();
+      sched_ds_mfma<D / 8, 1, 2>();
       k_product2<D>(G0, cv, gf, G1, cv + 32 * C::kVS, gf);
-      sched_ds_mfma<D / 8, 1, PCOPS_DQ_A>();
-#else
-      k_product<D>(S0, ck, qf);
-      k_product<D>(S1, ck + 32 * C::kKS, qf);
-      k_product<D>(G0, cv, gf);
-      k_product<D>(G1, cv + 32 * C::kVS, gf);
-#endif
-  #pragma unroll
+      sched_ds_mfma<D / 8, 1, 2>();
+#pragma unroll
       for (int r = 0; r < 16; ++r) {
         float p0 = exp2_ftz(__builtin_fmaf(S0[r], sl2, -lse2));
         float p1 = exp2_ftz(__builtin_fmaf(S1[r], sl2, -lse2));
@@ -967,7 +909,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OC
 // MODE 0: dK and dV in one pass (one wave per SIMD: both D x 32 accumulators
 // live).  MODE 1: dV only, MODE 2: dK only -- half the accumulators, so OCC = 2
 // waves per SIMD fit; the split pays one extra S recompute (5 instead of 4
-// GEMM units per key) for the second wave's latency hiding.
+// GEMM units per key) for the second wave's latency hiding.  MODE 0 is the
+// D <= 64 pass; MODE 1 + 2 run only as the D >= 96 fallback for row strides
+// attn_dkv3_kernel cannot address (launch_dkv_wide).
 template <int D, int NW, int MODE, int OCC, bool CS>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(OCC, OCC))) void attn_dkv2_kernel(const __bf16 *__restrict__ Q,
                                                             const __bf16 *__restrict__ K,
@@ -1160,28 +1104,14 @@ __device__ __forceinline__ void dkv3_rows(RowConsts &rc, const float *cl, const 
 // and an operand redefined by one can only be used after it.  pin() marks the
 // start of a chunk; the chunk's inputs pass through it and its outputs
 // through the next one, so each chunk's VALU and MFMA stay between the two.
-// Diagnostic ablations of the dK/dV v3 loop (tools/dkv3_probe.hip builds; 0 in the
-// product): 1 = B without exp / row constants, 2 = no C MFMAs, 4 = no A MFMAs
-#ifndef PCOPS_DKV3_ABL
-#define PCOPS_DKV3_ABL 0
-#endif
-#ifndef PCOPS_DS_NT
-#define PCOPS_DS_NT 1
-#endif
+//
 // Register pressure (round 6): the D = 128 body holds the next half's row fragments (64 VGPRs)
 // and C's transposed fragments (64) from early in the half, and the compiler moves ~64-87
-// values per tile between AGPRs and VGPRs to fit.  Reading them just in time instead
-// (PCOPS_DKV3_LA / _LAC = chunks of read-ahead) removes ~23 of those moves but exposes the LDS
-// latency: 1.43-1.47 -> 1.55-1.61 ms at 2048^2 (profiles/r6_dkv3_regpressure_ab.txt), so the
-// early reads stay (0 = the whole half's fragments at once).  S / dP as VGPR-form inline-asm
-// MFMAs (no v_accvgpr_read per score) did not fit either: the compiler spilled others instead.
-#ifndef PCOPS_DKV3_LA
-#define PCOPS_DKV3_LA 0
-#endif
-#ifndef PCOPS_DKV3_LAC
-#define PCOPS_DKV3_LAC 0
-#endif
-
+// values per tile between AGPRs and VGPRs to fit.  Reading them just in time instead (each
+// fragment a chunk or two ahead of its MFMA) removes ~23 of those moves but exposes the LDS
+// latency: 1.43-1.47 -> 1.55-1.61 ms at 2048^2 (profiles/r6_dkv3_regpressure_ab.txt), so a
+// half's fragments are read all at once.  S / dP as VGPR-form inline-asm MFMAs (no
+// v_accvgpr_read per score) did not fit either: the compiler spilled others instead.
 template <typename T>
 __device__ __forceinline__ void pin(T &x) {
   asm volatile("" : "+v"(x));
@@ -1193,30 +1123,6 @@ __device__ __forceinline__ void rows_frag(bf16x8 (&a)[D / 16], const __bf16 *lds
   const int l = lane_(), h = l >> 5, row = l & 31;
 #pragma unroll
   for (int s = 0; s < D / 16; ++s) a[s] = *reinterpret_cast<const bf16x8 *>(lds + img_off<D>(row, 2 * s + h));
-}
-
-// fragment f = s (D/32) + db of tr_frag (two ds_read_b64_tr_b16)
-template <int D>
-__device__ __forceinline__ bf16x8 tr_frag1(const __bf16 *lds, int f) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const int l = lane_(), h = l >> 5, g = (l >> 4) & 1, i = l & 15, q = i >> 2, p = i & 3;
-  const int s = f / (D / 32), db = f % (D / 32);
-  typedef __attribute__((address_space(3))) short4v lds_s4;
-  const int row0 = 16 * s + 4 * h + q;
-  const int ch = 4 * db + 2 * g + (p >> 1), e = 4 * (p & 1);
-  const short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4 *)(lds + img_off<D>(row0, ch) + e));
-  const short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4 *)(lds + img_off<D>(row0 + 8, ch) + e));
-  return __builtin_shufflevector(__builtin_bit_cast(bf16x4, lo), __builtin_bit_cast(bf16x4, hi), 0, 1, 2, 3, 4, 5, 6, 7);
-#else
-  return bf16x8{};
-#endif
-}
-
-// fragment s of rows_frag (one ds_read_b128)
-template <int D>
-__device__ __forceinline__ bf16x8 row_frag1(const __bf16 *lds, int s) {
-  const int l = lane_(), h = l >> 5, row = l & 31;
-  return *reinterpret_cast<const bf16x8 *>(lds + img_off<D>(row, 2 * s + h));
 }
 
 // the D/16 transposed fragments of a 32-row half (v_product's A operands, [s][db])
@@ -1249,14 +1155,14 @@ __device__ __forceinline__ float f4_at(const float4 &v, int i) {
 // [A(j+1) | B(j)] in D/16 chunks: chunk I = MFMA I of the S chain and of the dP
 // chain, plus B's rows [16 I / (D/16), 16 (I+1) / (D/16)) (whole bf16 pairs:
 // packed words pw / gw[r / 2]).  NEXT = false: B only.  The transposed reads of
-// C(j) are issued after chunk TRI so they land before C starts.
+// C(j) (hq / hg: this half's Q / dO rows) are issued after chunk D/32 so they land
+// before C starts.
 template <int D, bool NEXT, int I = 0>
 __device__ __forceinline__ void dkv3_ab(f32x16 &Sn, f32x16 &Gn, bf16x8 (&qa)[D / 16], bf16x8 (&ga)[D / 16],
                                         bf16x8 (&kf)[D / 16], bf16x8 (&vf)[D / 16], const f32x16 &S,
                                         const f32x16 &G, const RowConsts &rc, float sl2, unsigned (&pw)[8],
                                         unsigned (&gw)[8], bf16x8 (&va)[D / 16], bf16x8 (&ka)[D / 16],
-                                        const __bf16 *hq, const __bf16 *hg, const __bf16 *nq,
-                                        const __bf16 *ng) {
+                                        const __bf16 *hq, const __bf16 *hg) {
   if constexpr (I < D / 16) {
     constexpr int R0 = 2 * (8 * I / (D / 16)), R1 = 2 * (8 * (I + 1) / (D / 16));
     float la[16], da[16];
@@ -1267,13 +1173,7 @@ __device__ __forceinline__ void dkv3_ab(f32x16 &Sn, f32x16 &Gn, bf16x8 (&qa)[D /
       pin(la[r]);
       pin(da[r]);
     }
-    if constexpr (NEXT && PCOPS_DKV3_LA > 0 && I + PCOPS_DKV3_LA < D / 16) {
-      // the row fragments PCOPS_DKV3_LA chunks ahead (not all D/16 at the half's start: the
-      // 512-register body then spilled ~90 registers per tile through v_accvgpr moves)
-      qa[I + PCOPS_DKV3_LA] = row_frag1<D>(nq, I + PCOPS_DKV3_LA);
-      ga[I + PCOPS_DKV3_LA] = row_frag1<D>(ng, I + PCOPS_DKV3_LA);
-    }
-    if constexpr (NEXT && !(PCOPS_DKV3_ABL & 4)) {
+    if constexpr (NEXT) {
       pin(kf[I]);
       pin(vf[I]);
       Sn = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa[I], kf[I], Sn, 0, 0, 0);
@@ -1281,42 +1181,27 @@ __device__ __forceinline__ void dkv3_ab(f32x16 &Sn, f32x16 &Gn, bf16x8 (&qa)[D /
     }
 #pragma unroll
     for (int r = R0; r < R1; r += 2) {
-#if PCOPS_DKV3_ABL & 1
-      const bf16x2 pp = {(__bf16)S[r], (__bf16)S[r + 1]};
-      const bf16x2 gg = {(__bf16)G[r], (__bf16)G[r + 1]};
-#else
       const float p0 = exp2_ftz(__builtin_fmaf(S[r], sl2, -la[r]));  // 0 for rows beyond Lq (lse = +inf)
       const float p1 = exp2_ftz(__builtin_fmaf(S[r + 1], sl2, -la[r + 1]));
       const bf16x2 pp = {(__bf16)p0, (__bf16)p1};
       const bf16x2 gg = {(__bf16)(p0 * (G[r] - da[r])), (__bf16)(p1 * (G[r + 1] - da[r + 1]))};
-#endif
       pw[r / 2] = __builtin_bit_cast(unsigned, pp);
       gw[r / 2] = __builtin_bit_cast(unsigned, gg);
       pin(pw[r / 2]);
       pin(gw[r / 2]);
     }
-    if constexpr (PCOPS_DKV3_LAC > 0) {
-      // C's first transposed fragments, issued in the last chunks so they land before C
-      if constexpr (I == D / 16 - 1) {
-#pragma unroll
-        for (int f = 0; f < PCOPS_DKV3_LAC; ++f) {
-          va[f] = tr_frag1<D>(hg, f);
-          ka[f] = tr_frag1<D>(hq, f);
-        }
-      }
-    } else if constexpr (I == D / 32) {
+    if constexpr (I == D / 32) {
       tr_frag<D>(va, hg);
       tr_frag<D>(ka, hq);
     }
-    dkv3_ab<D, NEXT, I + 1>(Sn, Gn, qa, ga, kf, vf, S, G, rc, sl2, pw, gw, va, ka, hq, hg, nq, ng);
+    dkv3_ab<D, NEXT, I + 1>(Sn, Gn, qa, ga, kf, vf, S, G, rc, sl2, pw, gw, va, ka, hq, hg);
   }
 }
 
 // C(j): dV^T += dO^T P (va), dK^T += Q^T dS (ka), per accumulator in v_product's order
 template <int D>
 __device__ __forceinline__ void dkv3_c(f32x16 (&Y1)[D / 32], f32x16 (&Y2)[D / 32], bf16x8 (&va)[D / 16],
-                                       bf16x8 (&ka)[D / 16], const unsigned (&pw)[8], const unsigned (&gw)[8],
-                                       const __bf16 *hq, const __bf16 *hg) {
+                                       bf16x8 (&ka)[D / 16], const unsigned (&pw)[8], const unsigned (&gw)[8]) {
   bf16x8 pb[2], gb[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -1329,13 +1214,6 @@ __device__ __forceinline__ void dkv3_c(f32x16 (&Y1)[D / 32], f32x16 (&Y2)[D / 32
 #pragma unroll
     for (int db = 0; db < D / 32; ++db) {
       const int f = s * (D / 32) + db;
-      if constexpr (PCOPS_DKV3_LAC > 0) {
-        // the fragment PCOPS_DKV3_LAC steps ahead (C's first ones came with the AB phase)
-        if (f + PCOPS_DKV3_LAC < D / 16) {
-          va[f + PCOPS_DKV3_LAC] = tr_frag1<D>(hg, f + PCOPS_DKV3_LAC);
-          ka[f + PCOPS_DKV3_LAC] = tr_frag1<D>(hq, f + PCOPS_DKV3_LAC);
-        }
-      }
       Y1[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(va[f], pb[s], Y1[db], 0, 0, 0);
       Y2[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka[f], gb[s], Y2[db], 0, 0, 0);
     }
@@ -1493,24 +1371,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
     constexpr bool NEXT = decltype(next_c)::value;
     bf16x8 qa[D / 16], ga[D / 16];
     if constexpr (NEXT) {
-      if constexpr (PCOPS_DKV3_LA > 0) {
-#pragma unroll
-        for (int s0 = 0; s0 < PCOPS_DKV3_LA && s0 < D / 16; ++s0) {
-          qa[s0] = row_frag1<D>(nq, s0);
-          ga[s0] = row_frag1<D>(ng, s0);
-        }
-      } else {
-        rows_frag<D>(qa, nq);
-        rows_frag<D>(ga, ng);
-      }
+      rows_frag<D>(qa, nq);
+      rows_frag<D>(ga, ng);
     }
     RowConsts rc;
     dkv3_rows(rc, cl, cd);
     f32x16 Sn = f32x16{}, Gn = f32x16{};
     unsigned pw[8], gw[8];
     bf16x8 va[D / 16], ka[D / 16];
-    dkv3_ab<D, NEXT>(Sn, Gn, qa, ga, kf, vf, Sc, Gc, rc, sl2, pw, gw, va, ka, hq, hg, nq, ng);
-    if constexpr (!(PCOPS_DKV3_ABL & 2)) dkv3_c<D>(Y1, Y2, va, ka, pw, gw, hq, hg);
+    dkv3_ab<D, NEXT>(Sn, Gn, qa, ga, kf, vf, Sc, Gc, rc, sl2, pw, gw, va, ka, hq, hg);
+    dkv3_c<D>(Y1, Y2, va, ka, pw, gw);
     if constexpr (DS) {
       // lane (key, h) holds queries 8g + 4h + 0..3 (g = 0..3) as bf16 pairs gw[2g], gw[2g+1]:
       // one permlane32 swap per pair of words gives each lane two runs of 8 queries
@@ -1523,15 +1393,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC, OCC)))
       const auto a1 = __builtin_amdgcn_permlane32_swap(w[1], w[3], false, false);
       const auto b0 = __builtin_amdgcn_permlane32_swap(w[4], w[6], false, false);
       const auto b1 = __builtin_amdgcn_permlane32_swap(w[5], w[7], false, false);
-#if PCOPS_DS_NT
       // streaming stores: dS^T is read once, by the dQ kernel; keep the Q / dO tiles the
-      // key blocks of a head share in L2
+      // key blocks of a head share in L2 (with the dQ kernel's non-temporal loads 2.65 -> 2.53 ms
+      // for the hd-128 backward, profiles/r4_attn_ds_ab.txt)
       __builtin_nontemporal_store((u32x4){a0[0], a1[0], a0[1], a1[1]}, reinterpret_cast<u32x4 *>(ds_row + qh0));
       __builtin_nontemporal_store((u32x4){b0[0], b1[0], b0[1], b1[1]}, reinterpret_cast<u32x4 *>(ds_row + qh0 + 16));
-#else
-      *reinterpret_cast<u32x4 *>(ds_row + qh0) = (u32x4){a0[0], a1[0], a0[1], a1[1]};
-      *reinterpret_cast<u32x4 *>(ds_row + qh0 + 16) = (u32x4){b0[0], b1[0], b0[1], b1[1]};
-#endif
     }
     mid();
     Sc = Sn;
@@ -1664,11 +1530,7 @@ __global__ __launch_bounds__(512) void attn_dqs_kernel(const __bf16 *__restrict_
     for (int c = 0; c < kDC; ++c) {
       const int idx = threadIdx.x + c * NT;
       const bf16x8 *src = reinterpret_cast<const bf16x8 *>(Db + (long long)(k0 + (idx >> 5)) * ds_cols + (idx & 31) * 8);
-#if PCOPS_DS_NT
       dr[c] = __builtin_nontemporal_load(src);   // read once
-#else
-      dr[c] = *src;
-#endif
     }
   };
   auto store = [&](int slot) {
@@ -1709,222 +1571,119 @@ __global__ __launch_bounds__(512) void attn_dqs_kernel(const __bf16 *__restrict_
   }
 }
 
-// D = 64 runs 4-wave blocks at 3 waves per SIMD (the key-half split fits
-// 162 VGPRs): three independent blocks per CU instead of one 8-wave block.
-// PCOPS_DQ_NW4=0 keeps the 8-wave form (A/B).
+// dQ blocks: 8 waves at Lq > 128, 4 below (dq2_dispatch), except D = 64 and 96, which run
+// 4-wave blocks at any length.  D = 64 processes one 32-key half at a time (HS: 162 VGPRs) at 3
+// waves per SIMD: three independent blocks per CU instead of one 8-wave block (2048^2 0.536 ->
+// 0.503 ms, 2048 x 512 0.188 -> 0.149 ms).  D = 128 keeps 8 waves for long sequences: 4-wave
+// key-half blocks at any length measured the same (0.855 vs 0.845 ms,
+// profiles/r3_attn_occupancy_ab.txt); its 4-wave form is for short sequences only.
 template <int D, int NW>
 struct Dq2Cfg {
-  static constexpr bool kHS = (D == 64 || D == 128) && NW == 4;  // D = 128, NW = 4: short sequences only
+  static constexpr bool kHS = (D == 64 || D == 128) && NW == 4;
   static constexpr int kOcc = kHS ? (D == 64 ? 3 : 2) : (D <= 96 || NW == 8) ? 2 : 1;
 };
 
-// per-block column partial sums of the gradients a backward launch stores (the
-// *_colsum entry points): dQ in `a`; dK in `a`, dV in `b`; row (bh * nrb + rb) of
-// D floats each, nrb = the launch's row blocks per (batch, head), set by the launcher
-struct ColPart {
-  float *a = nullptr, *b = nullptr;
-  int nrb = 0;
-};
-
 template <int D, int NW, bool FD, bool CS>
-int launch_dq2_impl(const void *q, const void *k, const void *v, const void *dout, const float *lse,
-                    const float *delta, void *dq, int BH, int Lq, int Lk, float scale, const Strides &st,
-                    const void *o, float *delta_out, hipStream_t s, ColPart *cp) {
+int launch_dq2_impl(const AttnArgs &a) {
   using C = Fwd2Cfg<D, NW>;
   constexpr int OCC = Dq2Cfg<D, NW>::kOcc;
   constexpr bool HS = Dq2Cfg<D, NW>::kHS;
-  static const hipError_t attr = hipFuncSetAttribute((const void *)attn_dq2_kernel<D, NW, OCC, FD, HS, CS>,
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::kLds);
-  if (attr != hipSuccess) return PCOPS_ERR_LAUNCH;
-  const dim3 grid((Lq + NW * 32 - 1) / (NW * 32), BH);
-  if (cp) cp->nrb = grid.x;
-  hipLaunchKernelGGL((attn_dq2_kernel<D, NW, OCC, FD, HS, CS>), grid, dim3(C::kThr), C::kLds, s, (const __bf16 *)q,
-                     (const __bf16 *)k, (const __bf16 *)v, (const __bf16 *)dout, lse, delta, (__bf16 *)dq, Lq, Lk,
-                     scale, st, (const __bf16 *)o, delta_out, cp ? cp->a : nullptr);
-  PC_CHECK_LAUNCH();
-  return PCOPS_OK;
+  const dim3 grid((a.Lq + NW * 32 - 1) / (NW * 32), a.BH);
+  if (a.cp) a.cp->nrb = grid.x;
+  return launch_lds<attn_dq2_kernel<D, NW, OCC, FD, HS, CS>>(
+      grid, C::kThr, C::kLds, a.s, (const __bf16 *)a.q, (const __bf16 *)a.k, (const __bf16 *)a.v,
+      (const __bf16 *)a.dout, a.lse, a.delta, (__bf16 *)a.dq, a.Lq, a.Lk, a.scale, a.st, (const __bf16 *)a.o,
+      a.delta_out, a.cp ? a.cp->a : (float *)nullptr);
 }
 
-// o == nullptr: delta precomputed (read from `delta`); else fused, written to delta_out
+// a.o == nullptr: delta precomputed (read from a.delta); else fused, written to a.delta_out
 template <int D, int NW>
-int launch_dq2(const void *q, const void *k, const void *v, const void *dout, const float *lse, const float *delta,
-               void *dq, int BH, int Lq, int Lk, float scale, const Strides &st, hipStream_t s,
-               const void *o = nullptr, float *delta_out = nullptr, ColPart *cp = nullptr) {
-  if (cp) return o ? launch_dq2_impl<D, NW, true, true>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, scale, st, o, delta_out, s, cp)
-                  : PCOPS_ERR_UNSUPPORTED;  // the column sums ride on the fused-delta pass
-  return o ? launch_dq2_impl<D, NW, true, false>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, scale, st, o, delta_out, s, cp)
-           : launch_dq2_impl<D, NW, false, false>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, scale, st, o, delta_out, s, cp);
+int launch_dq2(const AttnArgs &a) {
+  if (a.cp) return a.o ? launch_dq2_impl<D, NW, true, true>(a)
+                       : PCOPS_ERR_UNSUPPORTED;  // the column sums ride on the fused-delta pass
+  return a.o ? launch_dq2_impl<D, NW, true, false>(a) : launch_dq2_impl<D, NW, false, false>(a);
 }
 
-bool dkv_split() {  // PCOPS_DKV_SPLIT=0 keeps the one-pass dK/dV kernel for D = 128 (A/B runs)
-  static const bool v = [] {
-    const char *e = getenv("PCOPS_DKV_SPLIT");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
-// one dK/dV launch of a given shape: NW waves per block, MODE (0 one pass, 3 one pass by
-// 32-query halves -- the same per-accumulator order as 0, half the live S / dP), OCC waves / SIMD
-template <int D, int NW, int MODE, int OCC, bool CS>
-int launch_dkv2_cfg(const void *q, const void *k, const void *v, const void *dout, const float *lse,
-                    const float *delta, void *dk, void *dv, int BH, int Lq, int Lk, float scale, const Strides &st,
-                    hipStream_t s, ColPart *cp) {
-  using C = Fwd2Cfg<D, NW>;
-  const size_t lds = C::kLds + 4 * kKT * sizeof(float);
-  static const hipError_t attr = hipFuncSetAttribute((const void *)attn_dkv2_kernel<D, NW, MODE, OCC, CS>,
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr != hipSuccess) return PCOPS_ERR_LAUNCH;
-  const dim3 grid((Lk + NW * 32 - 1) / (NW * 32), BH);
-  if (cp) cp->nrb = grid.x;
-  hipLaunchKernelGGL((attn_dkv2_kernel<D, NW, MODE, OCC, CS>), grid, dim3(C::kThr), lds, s, (const __bf16 *)q,
-                     (const __bf16 *)k, (const __bf16 *)v, (const __bf16 *)dout, lse, delta, (__bf16 *)dk,
-                     (__bf16 *)dv, Lq, Lk, scale, st, cp ? cp->a : nullptr, cp ? cp->b : nullptr);
-  PC_CHECK_LAUNCH();
-  return PCOPS_OK;
-}
-
-template <int D, int OCC, bool CS, bool DS = false>
-int launch_dkv3(const void *q, const void *k, const void *v, const void *dout, const float *lse, const float *delta,
-                void *dk, void *dv, int BH, int Lq, int Lk, float scale, const Strides &st, hipStream_t s,
-                ColPart *cp, __bf16 *dsT = nullptr, int ds_rows = 0, int ds_cols = 0) {
-  if ((long long)kKT * (st.q_srow > st.o_srow ? st.q_srow : st.o_srow) >= (1ll << 31)) return PCOPS_ERR_UNSUPPORTED;
-  const size_t lds = 6ull * kKT * Img<D>::RS * sizeof(__bf16) + 6 * kKT * sizeof(float);
-  static const hipError_t attr = hipFuncSetAttribute((const void *)attn_dkv3_kernel<D, OCC, CS, DS>,
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr != hipSuccess) return PCOPS_ERR_LAUNCH;
-  const dim3 grid((Lk + 127) / 128, BH);
-  if (cp) cp->nrb = grid.x;
-  hipLaunchKernelGGL((attn_dkv3_kernel<D, OCC, CS, DS>), grid, dim3(256), lds, s, (const __bf16 *)q,
-                     (const __bf16 *)k, (const __bf16 *)v, (const __bf16 *)dout, lse, delta, (__bf16 *)dk,
-                     (__bf16 *)dv, Lq, Lk, scale, st, cp ? cp->a : nullptr, cp ? cp->b : nullptr, dsT, ds_rows,
-                     ds_cols);
-  PC_CHECK_LAUNCH();
-  return PCOPS_OK;
-}
-
-// dK/dV pass selection: the pipelined one-pass v3 kernel for D = 96 / 128 (bitwise the
-// split v2 passes' results; A/B at the PCN shapes: 2048^2 hd128 1.51 -> 1.38 ms, 512^2
-// hd96 0.105 -> 0.089 ms).  D = 64 keeps the 8-wave v2 pass (v3 at one wave per SIMD:
-// 0.70 -> 1.0 ms).  PCOPS_DKV3: 0 = never v3, 1 = v3 for every D >= 64 (A/B runs).
-int dkv3_mode() {
-  static const int v = env_int("PCOPS_DKV3", -1);
-  return v;
-}
-
-template <int D, int NW, bool CS>
-int launch_dkv2_cs(const void *q, const void *k, const void *v, const void *dout, const float *lse, const float *delta,
-                void *dk, void *dv, int BH, int Lq, int Lk, float scale, const Strides &st, hipStream_t s,
-                ColPart *cp = nullptr) {
-  using C = Fwd2Cfg<D, NW>;
-  if constexpr (D >= 64) {
-    const int m3 = dkv3_mode();
-    if (m3 == 1 || (m3 < 0 && D >= 96)) {
-      const int rc = launch_dkv3<D, 1, CS>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp);
-      if (rc != PCOPS_ERR_UNSUPPORTED) return rc;  // strides too large for its 32-bit tile offsets: v2 below
-    }
-  }
-  if constexpr (D == 64 && NW == 8 && !CS) {
-    // occupancy variants of the long-sequence D = 64 pass (A/B: PCOPS_DKV64)
-    static const int var = env_int("PCOPS_DKV64", 0);
-    switch (var) {
-      case 1: return launch_dkv2_cfg<64, 4, 3, 2, CS>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp);
-      case 2: return launch_dkv2_cfg<64, 4, 3, 3, CS>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp);
-      case 3: return launch_dkv2_cfg<64, 8, 3, 2, CS>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp);
-      case 4: return launch_dkv2_cfg<64, 4, 0, 2, CS>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp);
-      default: break;
-    }
-  }
-  const size_t lds = C::kLds + 4 * kKT * sizeof(float);
-  const dim3 grid((Lk + NW * 32 - 1) / (NW * 32), BH);
-  if constexpr (D == 128 && !CS) {
-    // one-pass variants of the D = 128 dK/dV (A/B: PCOPS_DKV128): by 32-query halves, 1 wave per SIMD
-    static const int var = env_int("PCOPS_DKV128", 0);
-    if (var == 1) return launch_dkv2_cfg<128, 4, 3, 1, CS>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp);
-  }
-  if (D >= 96 && dkv_split()) {
-    // 8 waves per block halve each thread's share of the tile prefetch
-    using C8 = Fwd2Cfg<D, 8>;
-    const size_t lds8 = C8::kLds + 4 * kKT * sizeof(float);
-    const dim3 grid8((Lk + 8 * 32 - 1) / (8 * 32), BH);
-    if (cp) cp->nrb = grid8.x;
-    static const hipError_t a1 = hipFuncSetAttribute((const void *)attn_dkv2_kernel<D, 8, 1, 2, CS>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
-    static const hipError_t a2 = hipFuncSetAttribute((const void *)attn_dkv2_kernel<D, 8, 2, 2, CS>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
-    if (a1 != hipSuccess || a2 != hipSuccess) return PCOPS_ERR_LAUNCH;
-    hipLaunchKernelGGL((attn_dkv2_kernel<D, 8, 1, 2, CS>), grid8, dim3(C8::kThr), lds8, s, (const __bf16 *)q,
-                       (const __bf16 *)k, (const __bf16 *)v, (const __bf16 *)dout, lse, delta, (__bf16 *)dk,
-                       (__bf16 *)dv, Lq, Lk, scale, st, cp ? cp->a : nullptr, cp ? cp->b : nullptr);
-    PC_CHECK_LAUNCH();
-    hipLaunchKernelGGL((attn_dkv2_kernel<D, 8, 2, 2, CS>), grid8, dim3(C8::kThr), lds8, s, (const __bf16 *)q,
-                       (const __bf16 *)k, (const __bf16 *)v, (const __bf16 *)dout, lse, delta, (__bf16 *)dk,
-                       (__bf16 *)dv, Lq, Lk, scale, st, cp ? cp->a : nullptr, cp ? cp->b : nullptr);
-    PC_CHECK_LAUNCH();
-    return PCOPS_OK;
-  }
-  static const hipError_t attr = hipFuncSetAttribute((const void *)attn_dkv2_kernel<D, NW, 0, 1, CS>,
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr != hipSuccess) return PCOPS_ERR_LAUNCH;
-  if (cp) cp->nrb = grid.x;
-  hipLaunchKernelGGL((attn_dkv2_kernel<D, NW, 0, 1, CS>), grid, dim3(C::kThr), lds, s, (const __bf16 *)q,
-                     (const __bf16 *)k, (const __bf16 *)v, (const __bf16 *)dout, lse, delta, (__bf16 *)dk,
-                     (__bf16 *)dv, Lq, Lk, scale, st, cp ? cp->a : nullptr, cp ? cp->b : nullptr);
-  PC_CHECK_LAUNCH();
-  return PCOPS_OK;
-}
-
-template <int D, int NW>
-int launch_dkv2(const void *q, const void *k, const void *v, const void *dout, const float *lse, const float *delta,
-                void *dk, void *dv, int BH, int Lq, int Lk, float scale, const Strides &st, hipStream_t s,
-                ColPart *cp = nullptr) {
-  return cp ? launch_dkv2_cs<D, NW, true>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp)
-            : launch_dkv2_cs<D, NW, false>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp);
-}
-
-int dq2_dispatch(const void *q, const void *k, const void *v, const void *dout, const float *lse, const float *delta,
-                 void *dq, int BH, int Lq, int Lk, int D, float scale, const Strides &st, hipStream_t s,
-                 const void *o = nullptr, float *delta_out = nullptr, ColPart *cp = nullptr) {
-  const bool wide = Lq > 128;
+int dq2_dispatch(const AttnArgs &a, int D) {
+  const bool wide = a.Lq > 128;
   switch (D) {
     case 32:
-      return wide ? launch_dq2<32, 8>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, scale, st, s, o, delta_out, cp)
-                  : launch_dq2<32, 4>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, scale, st, s, o, delta_out, cp);
-    case 64: {
-      static const int nw4 = env_int("PCOPS_DQ_NW4", 1);
-      return (wide && !nw4) ? launch_dq2<64, 8>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, scale, st, s, o, delta_out, cp)
-                            : launch_dq2<64, 4>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, scale, st, s, o, delta_out, cp);
-    }
-    case 96:
-      return launch_dq2<96, 4>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, scale, st, s, o, delta_out, cp);
-    case 128: {
-      static const int nw4 = env_int("PCOPS_DQ128_NW4", 0);   // A/B: 4-wave key-half blocks at any length
-      return (wide && !nw4) ? launch_dq2<128, 8>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, scale, st, s, o, delta_out, cp)
-                            : launch_dq2<128, 4>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, scale, st, s, o, delta_out, cp);
-    }
-    default:
-      return PCOPS_ERR_UNSUPPORTED;
-  }
-}
-
-int dkv2_dispatch(const void *q, const void *k, const void *v, const void *dout, const float *lse, const float *delta,
-                  void *dk, void *dv, int BH, int Lq, int Lk, int D, float scale, const Strides &st, hipStream_t s,
-                  ColPart *cp = nullptr) {
-  const bool wide = Lk > 128;
-  switch (D) {
-    case 32:
-      return wide ? launch_dkv2<32, 8>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp)
-                  : launch_dkv2<32, 4>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp);
+      return wide ? launch_dq2<32, 8>(a) : launch_dq2<32, 4>(a);
     case 64:
-      return wide ? launch_dkv2<64, 8>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp)
-                  : launch_dkv2<64, 4>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp);
+      return launch_dq2<64, 4>(a);
     case 96:
-      return launch_dkv2<96, 4>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp);
+      return launch_dq2<96, 4>(a);
     case 128:
-      return launch_dkv2<128, 4>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cp);
+      return wide ? launch_dq2<128, 8>(a) : launch_dq2<128, 4>(a);
     default:
       return PCOPS_ERR_UNSUPPORTED;
   }
+}
+
+// one attn_dkv2_kernel launch: NW waves x 32 keys per block, MODE, OCC waves per SIMD
+template <int D, int NW, int MODE, int OCC, bool CS>
+int launch_dkv2(const AttnArgs &a) {
+  using C = Fwd2Cfg<D, NW>;
+  const size_t lds = C::kLds + 4 * kKT * sizeof(float);
+  const dim3 grid((a.Lk + NW * 32 - 1) / (NW * 32), a.BH);
+  if (a.cp) a.cp->nrb = grid.x;
+  return launch_lds<attn_dkv2_kernel<D, NW, MODE, OCC, CS>>(
+      grid, C::kThr, lds, a.s, (const __bf16 *)a.q, (const __bf16 *)a.k, (const __bf16 *)a.v,
+      (const __bf16 *)a.dout, a.lse, a.delta, (__bf16 *)a.dk, (__bf16 *)a.dv, a.Lq, a.Lk, a.scale, a.st,
+      a.cp ? a.cp->a : (float *)nullptr, a.cp ? a.cp->b : (float *)nullptr);
+}
+
+// the pipelined one-pass dK/dV; DS: also stores dS^T (ds_rows x ds_cols per head) for attn_dqs_kernel.
+// Its in-tile offsets are 32-bit: PCOPS_ERR_UNSUPPORTED when 64 row strides do not fit.
+template <int D, int OCC, bool CS, bool DS = false>
+int launch_dkv3(const AttnArgs &a, __bf16 *dsT = nullptr, int ds_rows = 0, int ds_cols = 0) {
+  if ((long long)kKT * (a.st.q_srow > a.st.o_srow ? a.st.q_srow : a.st.o_srow) >= (1ll << 31))
+    return PCOPS_ERR_UNSUPPORTED;
+  const size_t lds = 6ull * kKT * Img<D>::RS * sizeof(__bf16) + 6 * kKT * sizeof(float);
+  const dim3 grid((a.Lk + 127) / 128, a.BH);
+  if (a.cp) a.cp->nrb = grid.x;
+  return launch_lds<attn_dkv3_kernel<D, OCC, CS, DS>>(
+      grid, 256, lds, a.s, (const __bf16 *)a.q, (const __bf16 *)a.k, (const __bf16 *)a.v, (const __bf16 *)a.dout,
+      a.lse, a.delta, (__bf16 *)a.dk, (__bf16 *)a.dv, a.Lq, a.Lk, a.scale, a.st, a.cp ? a.cp->a : (float *)nullptr,
+      a.cp ? a.cp->b : (float *)nullptr, dsT, ds_rows, ds_cols);
+}
+
+// D = 96 / 128 dK/dV: the pipelined one-pass v3 kernel (against the split v2 passes at the PCN
+// shapes: 2048^2 hd128 1.51 -> 1.38 ms, 512^2 hd96 0.105 -> 0.089 ms, profiles/r3_dkv3_ab.txt).
+// Where it declines (64 x row stride >= 2^31) the split v2 pair runs instead, 8 waves per block
+// (they halve each thread's share of the tile prefetch): MODE 1 (dV) then MODE 2 (dK).  That is
+// the only path on such an input, and the only reason MODE 1 / 2 exist.
+template <int D, bool CS>
+int launch_dkv_wide(const AttnArgs &a) {
+  int rc = launch_dkv3<D, 1, CS>(a);
+  if (rc != PCOPS_ERR_UNSUPPORTED) return rc;
+  rc = launch_dkv2<D, 8, 1, 2, CS>(a);
+  return rc ? rc : launch_dkv2<D, 8, 2, 2, CS>(a);
+}
+
+// dK/dV blocks at D <= 64: one 8-wave v2 pass (MODE 0) at Lk > 128, 4 waves below.  D = 64 keeps
+// it over v3, which at one wave per SIMD measured 0.70 -> 1.0 ms (profiles/r3_dkv3_ab.txt), and
+// over the 4-wave / by-halves occupancy variants (0.703 -> 0.723-0.766 ms,
+// profiles/r3_attn_occupancy_ab.txt).
+template <bool CS>
+int dkv2_dispatch_cs(const AttnArgs &a, int D) {
+  const bool wide = a.Lk > 128;
+  switch (D) {
+    case 32:
+      return wide ? launch_dkv2<32, 8, 0, 1, CS>(a) : launch_dkv2<32, 4, 0, 1, CS>(a);
+    case 64:
+      return wide ? launch_dkv2<64, 8, 0, 1, CS>(a) : launch_dkv2<64, 4, 0, 1, CS>(a);
+    case 96:
+      return launch_dkv_wide<96, CS>(a);
+    case 128:
+      return launch_dkv_wide<128, CS>(a);
+    default:
+      return PCOPS_ERR_UNSUPPORTED;
+  }
+}
+
+int dkv2_dispatch(const AttnArgs &a, int D) {
+  return a.cp ? dkv2_dispatch_cs<true>(a, D) : dkv2_dispatch_cs<false>(a, D);
 }
 
 // dS^T buffer geometry of the D >= 96 path: rows = the dK/dV pass's key blocks (128),
@@ -1935,145 +1694,104 @@ struct DsGeom {
   unsigned long long bytes(int BH) const { return (unsigned long long)BH * rows * cols * sizeof(__bf16); }
 };
 
-// PCOPS_ATTN_DS=0 keeps the recomputing dQ pass for D >= 96 (A/B runs)
-bool ds_path_on() {
-  static const bool v = env_int("PCOPS_ATTN_DS", 1) != 0;
-  return v;
-}
-
+// the one-call backward at D >= 96: delta, dK/dV (+ dS^T), dQ from dS^T.  a.cp: the dK/dV sums,
+// cpq: the dQ sums; a.delta == a.delta_out (written first, then read)
 template <int D, bool CS>
-int launch_bwd_ds(const void *q, const void *k, const void *v, const void *o, const void *dout, const float *lse,
-                  void *dq, void *dk, void *dv, int BH, int Lq, int Lk, float scale, const Strides &st, hipStream_t s,
-                  float *delta, __bf16 *dsT, ColPart *cpq, ColPart *cpkv) {
-  const DsGeom gm(Lq, Lk);
-  const long long rows = (long long)BH * Lq;
-  hipLaunchKernelGGL((attn_delta2_kernel<D>), dim3((unsigned)((rows + 127) / 128)), dim3(256), 0, s,
-                     (const __bf16 *)o, (const __bf16 *)dout, delta, BH, Lq, st);
+int launch_bwd_ds(const AttnArgs &a, __bf16 *dsT, ColPart *cpq) {
+  const DsGeom gm(a.Lq, a.Lk);
+  const long long rows = (long long)a.BH * a.Lq;
+  hipLaunchKernelGGL((attn_delta2_kernel<D>), dim3((unsigned)((rows + 127) / 128)), dim3(256), 0, a.s,
+                     (const __bf16 *)a.o, (const __bf16 *)a.dout, a.delta_out, a.BH, a.Lq, a.st);
   PC_CHECK_LAUNCH();
-  int rc = launch_dkv3<D, 1, CS, true>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, scale, st, s, cpkv, dsT,
-                                       gm.rows, gm.cols);
+  const int rc = launch_dkv3<D, 1, CS, true>(a, dsT, gm.rows, gm.cols);
   if (rc) return rc;
   constexpr size_t lds = 2ull * kKT * (Img<D>::RS + kDsRS) * sizeof(__bf16);
-  static const hipError_t attr = hipFuncSetAttribute((const void *)attn_dqs_kernel<D, CS>,
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (attr != hipSuccess) return PCOPS_ERR_LAUNCH;
-  const dim3 grid((Lq + 255) / 256, BH);
+  const dim3 grid((a.Lq + 255) / 256, a.BH);
   if (cpq) cpq->nrb = grid.x;
-  hipLaunchKernelGGL((attn_dqs_kernel<D, CS>), grid, dim3(512), lds, s, (const __bf16 *)k, (const __bf16 *)dsT,
-                     (__bf16 *)dq, Lq, Lk, scale, st, gm.rows, gm.cols, cpq ? cpq->a : nullptr);
-  PC_CHECK_LAUNCH();
-  return PCOPS_OK;
+  return launch_lds<attn_dqs_kernel<D, CS>>(grid, 512, lds, a.s, (const __bf16 *)a.k, (const __bf16 *)dsT,
+                                            (__bf16 *)a.dq, a.Lq, a.Lk, a.scale, a.st, gm.rows, gm.cols,
+                                            cpq ? cpq->a : (float *)nullptr);
 }
 
-int fwd2_dispatch(const void *q, const void *k, const void *v, void *o, float *lse, int BH, int Lq, int Lk, int D,
-                  float scale, const Strides &st, hipStream_t s) {
-  const bool wide = Lq > 128;
+int fwd2_dispatch(const AttnArgs &a, int D) {
+  const bool wide = a.Lq > 128;
   switch (D) {
     case 32:
-      return wide ? launch_fwd2<32, 8>(q, k, v, o, lse, BH, Lq, Lk, scale, st, s)
-                  : launch_fwd2<32, 4>(q, k, v, o, lse, BH, Lq, Lk, scale, st, s);
+      return wide ? launch_fwd2<32, 8>(a) : launch_fwd2<32, 4>(a);
     case 64:
-      return wide ? launch_fwd2<64, 8>(q, k, v, o, lse, BH, Lq, Lk, scale, st, s)
-                  : launch_fwd2<64, 4>(q, k, v, o, lse, BH, Lq, Lk, scale, st, s);
-    case 96:
-      return wide ? launch_fwd2<96, 8>(q, k, v, o, lse, BH, Lq, Lk, scale, st, s)
-                  : launch_fwd2<96, 4>(q, k, v, o, lse, BH, Lq, Lk, scale, st, s);
+      return wide ? launch_fwd2<64, 8>(a) : launch_fwd2<64, 4>(a);
+    case 96:  // 4-wave blocks at any length (see launch_fwd2)
+      return launch_fwd2<96, 4>(a);
     case 128:
-      return wide ? launch_fwd2<128, 8>(q, k, v, o, lse, BH, Lq, Lk, scale, st, s)
-                  : launch_fwd2<128, 4>(q, k, v, o, lse, BH, Lq, Lk, scale, st, s);
+      return wide ? launch_fwd2<128, 8>(a) : launch_fwd2<128, 4>(a);
     default:
       return PCOPS_ERR_UNSUPPORTED;
   }
 }
 
-bool use_v1() {
-  static const int v = [] {
-    const char *e = getenv("PCOPS_ATTN_V1");
-    return (e && e[0] == '1') ? 1 : 0;
-  }();
-  return v != 0;
-}
-
-bool aligned_ok(const void *p, long long sb, long long sh, long long srow, int esize) {
-  const int vec = 16 / esize;
-  return ((uintptr_t)p % 16 == 0) && (sb % vec == 0) && (sh % vec == 0) && (srow % vec == 0);
-}
-
-template <typename T>
-int launch_fwd(const void *q, const void *k, const void *v, void *o, float *lse, int BH, int Lq, int Lk, int D,
-               float scale, const Strides &st, hipStream_t s) {
-  const dim3 grid((Lq + kWaves * 32 - 1) / (kWaves * 32), BH);
-#define ATT_FWD(DD)                                                                                           \
-  case DD:                                                                                                    \
-    hipLaunchKernelGGL((attn_fwd_kernel<T, DD>), grid, dim3(kThreads), 0, s, (const T *)q, (const T *)k,     \
-                       (const T *)v, (T *)o, lse, Lq, Lk, scale, st);                                         \
-    break;
-  switch (D) {
-    ATT_FWD(32)
-    ATT_FWD(64)
-    ATT_FWD(96)
-    ATT_FWD(128)
-    default:
-      return PCOPS_ERR_UNSUPPORTED;
+// ----------------------------------------------------------------- fp32 (first-generation kernels)
+#define ATT_F32_CASES(LAUNCH) \
+  switch (D) {                \
+    case 32:                  \
+      LAUNCH(32);             \
+      break;                  \
+    case 64:                  \
+      LAUNCH(64);             \
+      break;                  \
+    case 96:                  \
+      LAUNCH(96);             \
+      break;                  \
+    case 128:                 \
+      LAUNCH(128);            \
+      break;                  \
+    default:                  \
+      return PCOPS_ERR_UNSUPPORTED; \
   }
+
+int launch_fwd_f32(const AttnArgs &a, int D) {
+  const dim3 grid((a.Lq + kWaves * 32 - 1) / (kWaves * 32), a.BH);
+#define ATT_FWD(DD)                                                                                         \
+  hipLaunchKernelGGL((attn_fwd_kernel<float, DD>), grid, dim3(kThreads), 0, a.s, (const float *)a.q,       \
+                     (const float *)a.k, (const float *)a.v, (float *)a.out, a.lse_out, a.Lq, a.Lk, a.scale, a.st)
+  ATT_F32_CASES(ATT_FWD)
 #undef ATT_FWD
   PC_CHECK_LAUNCH();
   return PCOPS_OK;
 }
 
 template <typename T>
-int launch_delta(const void *o, const void *dout, float *delta, int BH, int Lq, int D, const Strides &st,
-                 hipStream_t s) {
-  const int rows = BH * Lq;
-  hipLaunchKernelGGL((attn_delta_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, s, (const T *)o, (const T *)dout,
-                     delta, BH, Lq, D, st);
+int launch_delta(const AttnArgs &a, int D) {
+  const int rows = a.BH * a.Lq;
+  hipLaunchKernelGGL((attn_delta_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, a.s, (const T *)a.o,
+                     (const T *)a.dout, a.delta_out, a.BH, a.Lq, D, a.st);
   PC_CHECK_LAUNCH();
   return PCOPS_OK;
 }
 
-template <typename T>
-int launch_dq(const void *q, const void *k, const void *v, const void *dout, const float *lse, const float *delta,
-              void *dq, int BH, int Lq, int Lk, int D, float scale, const Strides &st, hipStream_t s) {
-  const dim3 gq((Lq + kWaves * 32 - 1) / (kWaves * 32), BH);
-#define ATT_DQ(DD)                                                                                              \
-  case DD:                                                                                                      \
-    hipLaunchKernelGGL((attn_dq_kernel<T, DD>), gq, dim3(kThreads), 0, s, (const T *)q, (const T *)k,           \
-                       (const T *)v, (const T *)dout, lse, delta, (T *)dq, Lq, Lk, scale, st);                  \
-    break;
-  switch (D) {
-    ATT_DQ(32)
-    ATT_DQ(64)
-    ATT_DQ(96)
-    ATT_DQ(128)
-    default:
-      return PCOPS_ERR_UNSUPPORTED;
-  }
+int launch_dq_f32(const AttnArgs &a, int D) {
+  const dim3 gq((a.Lq + kWaves * 32 - 1) / (kWaves * 32), a.BH);
+#define ATT_DQ(DD)                                                                                          \
+  hipLaunchKernelGGL((attn_dq_kernel<float, DD>), gq, dim3(kThreads), 0, a.s, (const float *)a.q,          \
+                     (const float *)a.k, (const float *)a.v, (const float *)a.dout, a.lse, a.delta,        \
+                     (float *)a.dq, a.Lq, a.Lk, a.scale, a.st)
+  ATT_F32_CASES(ATT_DQ)
 #undef ATT_DQ
   PC_CHECK_LAUNCH();
   return PCOPS_OK;
 }
 
-template <typename T>
-int launch_dkv(const void *q, const void *k, const void *v, const void *dout, const float *lse, const float *delta,
-               void *dk, void *dv, int BH, int Lq, int Lk, int D, float scale, const Strides &st, hipStream_t s) {
-  const dim3 gk((Lk + kWaves * 32 - 1) / (kWaves * 32), BH);
-#define ATT_DKV(DD)                                                                                             \
-  case DD:                                                                                                      \
-    hipLaunchKernelGGL((attn_dkv_kernel<T, DD>), gk, dim3(kThreads), 0, s, (const T *)q, (const T *)k,          \
-                       (const T *)v, (const T *)dout, lse, delta, (T *)dk, (T *)dv, Lq, Lk, scale, st);         \
-    break;
-  switch (D) {
-    ATT_DKV(32)
-    ATT_DKV(64)
-    ATT_DKV(96)
-    ATT_DKV(128)
-    default:
-      return PCOPS_ERR_UNSUPPORTED;
-  }
+int launch_dkv_f32(const AttnArgs &a, int D) {
+  const dim3 gk((a.Lk + kWaves * 32 - 1) / (kWaves * 32), a.BH);
+#define ATT_DKV(DD)                                                                                         \
+  hipLaunchKernelGGL((attn_dkv_kernel<float, DD>), gk, dim3(kThreads), 0, a.s, (const float *)a.q,         \
+                     (const float *)a.k, (const float *)a.v, (const float *)a.dout, a.lse, a.delta,        \
+                     (float *)a.dk, (float *)a.dv, a.Lq, a.Lk, a.scale, a.st)
+  ATT_F32_CASES(ATT_DKV)
 #undef ATT_DKV
   PC_CHECK_LAUNCH();
   return PCOPS_OK;
 }
+#undef ATT_F32_CASES
 
 // out_s[c] = sum over r < n of part_s[r * C + c] for one or two (part, out) segments
 // (the per-block partial rows of dQ, or of dK and dV, C = H * D): 32 columns x 32 row
@@ -2116,30 +1834,61 @@ int check_common(int BH, int Lq, int Lk, int D, int dtype) {
   return PCOPS_OK;
 }
 
+bool aligned_ok(const void *p, long long sb, long long sh, long long srow, int esize) {
+  const int vec = 16 / esize;
+  return ((uintptr_t)p % 16 == 0) && (sb % vec == 0) && (sh % vec == 0) && (srow % vec == 0);
+}
+
+// A pointer an entry point requires, and the strides it is addressed with (kPlain: none --
+// lse, the delta pass's operands, a workspace: only checked for null)
+enum Layout { kAsQ, kAsK, kAsV, kAsO, kPlain };
+struct Req {
+  const void *p;
+  Layout as;
+};
+
+// The entry points' argument checks, in the order their return codes are specified: a null
+// pointer is INVALID; then a missing or short workspace (ws_need > 0) is WORKSPACE; then a base
+// or stride off the 16-byte vector grid (es = element size) is UNSUPPORTED.
+int validate(std::initializer_list<Req> reqs, const Strides &st, int es, const void *ws = nullptr,
+             unsigned long long ws_bytes = 0, unsigned long long ws_need = 0) {
+  for (const Req &r : reqs)
+    if (!r.p) return PCOPS_ERR_INVALID;
+  if (ws_need && (!ws || ws_bytes < ws_need)) return PCOPS_ERR_WORKSPACE;
+  for (const Req &r : reqs) {
+    const bool ok = r.as == kAsQ   ? aligned_ok(r.p, st.q_sb, st.q_sh, st.q_srow, es)
+                    : r.as == kAsK ? aligned_ok(r.p, st.k_sb, st.k_sh, st.k_srow, es)
+                    : r.as == kAsV ? aligned_ok(r.p, st.v_sb, st.v_sh, st.v_srow, es)
+                    : r.as == kAsO ? aligned_ok(r.p, st.o_sb, st.o_sh, st.o_srow, es)
+                                   : true;
+    if (!ok) return PCOPS_ERR_UNSUPPORTED;
+  }
+  return PCOPS_OK;
+}
+
 }  // namespace
 
 #define PC_ATTN_STRIDES                                                                                     \
   long long q_sb, long long q_sh, long long q_srow, long long k_sb, long long k_sh, long long k_srow, long long v_sb, \
       long long v_sh, long long v_srow, long long o_sb, long long o_sh, long long o_srow
 #define PC_ATTN_STRIDE_ARGS q_sb, q_sh, q_srow, k_sb, k_sh, k_srow, v_sb, v_sh, v_srow, o_sb, o_sh, o_srow
+// the fields every pass shares, as AttnArgs' leading members
+#define PC_ATTN_ARGS q, k, v, B * H, Lq, Lk, scale, Strides{PC_ATTN_STRIDE_ARGS, H}, (hipStream_t)stream
 
 extern "C" int pcops_attention_forward(const void *q, const void *k, const void *v, void *o, float *lse, int B, int H,
                                        int Lq, int Lk, int D, float scale, int dtype, PC_ATTN_STRIDES,
                                        pcops_stream_t stream) {
   if (B < 0 || H <= 0 || Lq < 0 || Lk < 0) return PCOPS_ERR_INVALID;
-  const int BH = B * H;
-  if (BH == 0 || Lq == 0) return PCOPS_OK;
-  if (Lk <= 0 || !q || !k || !v || !o) return PCOPS_ERR_INVALID;
+  if (B * H == 0 || Lq == 0) return PCOPS_OK;
+  if (Lk <= 0) return PCOPS_ERR_INVALID;
+  AttnArgs a{PC_ATTN_ARGS};
+  a.out = o;
+  a.lse_out = lse;
+  // a bad D or dtype is UNSUPPORTED as well, so checking it after the alignment changes no result
+  const int rc = validate({{q, kAsQ}, {k, kAsK}, {v, kAsV}, {o, kAsO}}, a.st, dtype == 0 ? 4 : 2);
+  if (rc) return rc;
   if (D % 32 != 0 || D > 128 || (dtype != 0 && dtype != 1)) return PCOPS_ERR_UNSUPPORTED;
-  const int es = dtype == 0 ? 4 : 2;
-  if (!aligned_ok(q, q_sb, q_sh, q_srow, es) || !aligned_ok(k, k_sb, k_sh, k_srow, es) ||
-      !aligned_ok(v, v_sb, v_sh, v_srow, es) || !aligned_ok(o, o_sb, o_sh, o_srow, es))
-    return PCOPS_ERR_UNSUPPORTED;
-  const Strides st{PC_ATTN_STRIDE_ARGS, H};
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == 0) return launch_fwd<float>(q, k, v, o, lse, BH, Lq, Lk, D, scale, st, s);
-  if (use_v1()) return launch_fwd<__bf16>(q, k, v, o, lse, BH, Lq, Lk, D, scale, st, s);
-  return fwd2_dispatch(q, k, v, o, lse, BH, Lq, Lk, D, scale, st, s);
+  return dtype == 0 ? launch_fwd_f32(a, D) : fwd2_dispatch(a, D);
 }
 
 extern "C" unsigned long long pcops_attention_bwd_workspace_bytes(int B, int H, int Lq, int Lk, int D) {
@@ -2155,14 +1904,16 @@ extern "C" int pcops_attention_bwd_preprocess(const void *o, const void *dout, i
   if (B < 0 || H <= 0 || Lq < 0) return PCOPS_ERR_INVALID;
   int rc = check_common(B * H, Lq, 1, D, dtype);
   if (rc) return rc;
-  const int BH = B * H;
-  if (BH == 0 || Lq == 0) return PCOPS_OK;
-  if (!o || !dout) return PCOPS_ERR_INVALID;
-  if (!workspace || workspace_bytes < pcops_attention_bwd_workspace_bytes(B, H, Lq, 1, D)) return PCOPS_ERR_WORKSPACE;
-  const Strides st{0, 0, 0, 0, 0, 0, 0, 0, 0, o_sb, o_sh, o_srow, H};
-  hipStream_t s = (hipStream_t)stream;
-  return dtype == 0 ? launch_delta<float>(o, dout, (float *)workspace, BH, Lq, D, st, s)
-                    : launch_delta<__bf16>(o, dout, (float *)workspace, BH, Lq, D, st, s);
+  if (B * H == 0 || Lq == 0) return PCOPS_OK;
+  AttnArgs a{nullptr, nullptr, nullptr, B * H, Lq, 0, 0.f, Strides{0, 0, 0, 0, 0, 0, 0, 0, 0, o_sb, o_sh, o_srow, H},
+             (hipStream_t)stream};
+  a.o = o;
+  a.dout = dout;
+  a.delta_out = (float *)workspace;
+  rc = validate({{o, kPlain}, {dout, kPlain}}, a.st, dtype == 0 ? 4 : 2, workspace, workspace_bytes,
+                pcops_attention_bwd_workspace_bytes(B, H, Lq, 1, D));
+  if (rc) return rc;
+  return dtype == 0 ? launch_delta<float>(a, D) : launch_delta<__bf16>(a, D);
 }
 
 extern "C" int pcops_attention_bwd_dq(const void *q, const void *k, const void *v, const void *dout, const float *lse,
@@ -2172,21 +1923,17 @@ extern "C" int pcops_attention_bwd_dq(const void *q, const void *k, const void *
   if (B < 0 || H <= 0) return PCOPS_ERR_INVALID;
   int rc = check_common(B * H, Lq, Lk, D, dtype);
   if (rc) return rc;
-  const int BH = B * H;
-  if (BH == 0 || Lq == 0) return PCOPS_OK;
-  if (!q || !k || !v || !dout || !lse || !dq || Lk <= 0) return PCOPS_ERR_INVALID;
-  if (!workspace || workspace_bytes < pcops_attention_bwd_workspace_bytes(B, H, Lq, Lk, D)) return PCOPS_ERR_WORKSPACE;
-  const int es = dtype == 0 ? 4 : 2;
-  if (!aligned_ok(q, q_sb, q_sh, q_srow, es) || !aligned_ok(k, k_sb, k_sh, k_srow, es) ||
-      !aligned_ok(v, v_sb, v_sh, v_srow, es) || !aligned_ok(dout, o_sb, o_sh, o_srow, es) ||
-      !aligned_ok(dq, q_sb, q_sh, q_srow, es))
-    return PCOPS_ERR_UNSUPPORTED;
-  const Strides st{PC_ATTN_STRIDE_ARGS, H};
-  hipStream_t s = (hipStream_t)stream;
-  const float *delta = (const float *)workspace;
-  if (dtype == 0) return launch_dq<float>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, D, scale, st, s);
-  if (use_v1()) return launch_dq<__bf16>(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, D, scale, st, s);
-  return dq2_dispatch(q, k, v, dout, lse, delta, dq, BH, Lq, Lk, D, scale, st, s);
+  if (B * H == 0 || Lq == 0) return PCOPS_OK;
+  if (Lk <= 0) return PCOPS_ERR_INVALID;
+  AttnArgs a{PC_ATTN_ARGS};
+  a.dout = dout;
+  a.lse = lse;
+  a.delta = (const float *)workspace;
+  a.dq = dq;
+  rc = validate({{q, kAsQ}, {k, kAsK}, {v, kAsV}, {dout, kAsO}, {lse, kPlain}, {dq, kAsQ}}, a.st, dtype == 0 ? 4 : 2,
+                workspace, workspace_bytes, pcops_attention_bwd_workspace_bytes(B, H, Lq, Lk, D));
+  if (rc) return rc;
+  return dtype == 0 ? launch_dq_f32(a, D) : dq2_dispatch(a, D);
 }
 
 extern "C" int pcops_attention_bwd_dq_delta(const void *q, const void *k, const void *v, const void *o,
@@ -2196,24 +1943,25 @@ extern "C" int pcops_attention_bwd_dq_delta(const void *q, const void *k, const 
   if (B < 0 || H <= 0) return PCOPS_ERR_INVALID;
   int rc = check_common(B * H, Lq, Lk, D, dtype);
   if (rc) return rc;
-  const int BH = B * H;
-  if (BH == 0 || Lq == 0) return PCOPS_OK;
-  if (dtype == 0 || use_v1()) {  // fp32 / first-generation kernels: the two-launch form
+  if (B * H == 0 || Lq == 0) return PCOPS_OK;
+  if (dtype == 0) {  // fp32 (first-generation kernels): the two-launch form
     rc = pcops_attention_bwd_preprocess(o, dout, B, H, Lq, D, dtype, o_sb, o_sh, o_srow, workspace, workspace_bytes,
                                         stream);
     if (rc) return rc;
     return pcops_attention_bwd_dq(q, k, v, dout, lse, dq, B, H, Lq, Lk, D, scale, dtype, PC_ATTN_STRIDE_ARGS,
                                   workspace, workspace_bytes, stream);
   }
-  if (!q || !k || !v || !o || !dout || !lse || !dq || Lk <= 0) return PCOPS_ERR_INVALID;
-  if (!workspace || workspace_bytes < pcops_attention_bwd_workspace_bytes(B, H, Lq, Lk, D)) return PCOPS_ERR_WORKSPACE;
-  if (!aligned_ok(q, q_sb, q_sh, q_srow, 2) || !aligned_ok(k, k_sb, k_sh, k_srow, 2) ||
-      !aligned_ok(v, v_sb, v_sh, v_srow, 2) || !aligned_ok(dout, o_sb, o_sh, o_srow, 2) ||
-      !aligned_ok(o, o_sb, o_sh, o_srow, 2) || !aligned_ok(dq, q_sb, q_sh, q_srow, 2))
-    return PCOPS_ERR_UNSUPPORTED;
-  const Strides st{PC_ATTN_STRIDE_ARGS, H};
-  return dq2_dispatch(q, k, v, dout, lse, nullptr, dq, BH, Lq, Lk, D, scale, st, (hipStream_t)stream, o,
-                      (float *)workspace);
+  if (Lk <= 0) return PCOPS_ERR_INVALID;
+  AttnArgs a{PC_ATTN_ARGS};
+  a.o = o;
+  a.dout = dout;
+  a.lse = lse;
+  a.delta_out = (float *)workspace;
+  a.dq = dq;
+  rc = validate({{q, kAsQ}, {k, kAsK}, {v, kAsV}, {o, kAsO}, {dout, kAsO}, {lse, kPlain}, {dq, kAsQ}}, a.st, 2,
+                workspace, workspace_bytes, pcops_attention_bwd_workspace_bytes(B, H, Lq, Lk, D));
+  if (rc) return rc;
+  return dq2_dispatch(a, D);
 }
 
 extern "C" int pcops_attention_bwd_dkv(const void *q, const void *k, const void *v, const void *dout,
@@ -2223,21 +1971,18 @@ extern "C" int pcops_attention_bwd_dkv(const void *q, const void *k, const void 
   if (B < 0 || H <= 0) return PCOPS_ERR_INVALID;
   int rc = check_common(B * H, Lq, Lk, D, dtype);
   if (rc) return rc;
-  const int BH = B * H;
-  if (BH == 0 || Lk == 0) return PCOPS_OK;
-  if (!q || !k || !v || !dout || !lse || !dk || !dv || Lq <= 0) return PCOPS_ERR_INVALID;
-  if (!workspace || workspace_bytes < pcops_attention_bwd_workspace_bytes(B, H, Lq, Lk, D)) return PCOPS_ERR_WORKSPACE;
-  const int es = dtype == 0 ? 4 : 2;
-  if (!aligned_ok(q, q_sb, q_sh, q_srow, es) || !aligned_ok(k, k_sb, k_sh, k_srow, es) ||
-      !aligned_ok(v, v_sb, v_sh, v_srow, es) || !aligned_ok(dout, o_sb, o_sh, o_srow, es) ||
-      !aligned_ok(dk, k_sb, k_sh, k_srow, es) || !aligned_ok(dv, v_sb, v_sh, v_srow, es))
-    return PCOPS_ERR_UNSUPPORTED;
-  const Strides st{PC_ATTN_STRIDE_ARGS, H};
-  hipStream_t s = (hipStream_t)stream;
-  const float *delta = (const float *)workspace;
-  if (dtype == 0) return launch_dkv<float>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, D, scale, st, s);
-  if (use_v1()) return launch_dkv<__bf16>(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, D, scale, st, s);
-  return dkv2_dispatch(q, k, v, dout, lse, delta, dk, dv, BH, Lq, Lk, D, scale, st, s);
+  if (B * H == 0 || Lk == 0) return PCOPS_OK;
+  if (Lq <= 0) return PCOPS_ERR_INVALID;
+  AttnArgs a{PC_ATTN_ARGS};
+  a.dout = dout;
+  a.lse = lse;
+  a.delta = (const float *)workspace;
+  a.dk = dk;
+  a.dv = dv;
+  rc = validate({{q, kAsQ}, {k, kAsK}, {v, kAsV}, {dout, kAsO}, {lse, kPlain}, {dk, kAsK}, {dv, kAsV}}, a.st,
+                dtype == 0 ? 4 : 2, workspace, workspace_bytes, pcops_attention_bwd_workspace_bytes(B, H, Lq, Lk, D));
+  if (rc) return rc;
+  return dtype == 0 ? launch_dkv_f32(a, D) : dkv2_dispatch(a, D);
 }
 
 // The same two passes, each also forming the column sums of the gradients it
@@ -2257,24 +2002,26 @@ extern "C" int pcops_attention_bwd_dq_delta_colsum(const void *q, const void *k,
   if (B < 0 || H <= 0) return PCOPS_ERR_INVALID;
   int rc = check_common(B * H, Lq, Lk, D, dtype);
   if (rc) return rc;
-  if (dtype != 1 || use_v1()) return PCOPS_ERR_UNSUPPORTED;  // the bf16 MFMA passes only
-  const int BH = B * H;
+  if (dtype != 1) return PCOPS_ERR_UNSUPPORTED;  // the bf16 MFMA passes only
   if (!dq_colsum) return PCOPS_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  if (BH == 0) return PCOPS_OK;
+  if (B * H == 0) return PCOPS_OK;
   if (Lq == 0) return pc_memset_async(dq_colsum, 0, (size_t)H * D * sizeof(float), s) == hipSuccess ? PCOPS_OK
                                                                                               : PCOPS_ERR_LAUNCH;
-  if (!q || !k || !v || !o || !dout || !lse || !dq || Lk <= 0) return PCOPS_ERR_INVALID;
-  if (!workspace || workspace_bytes < pcops_attention_bwd_colsum_workspace_bytes(B, H, Lq, Lk, D))
-    return PCOPS_ERR_WORKSPACE;
-  if (!aligned_ok(q, q_sb, q_sh, q_srow, 2) || !aligned_ok(k, k_sb, k_sh, k_srow, 2) ||
-      !aligned_ok(v, v_sb, v_sh, v_srow, 2) || !aligned_ok(dout, o_sb, o_sh, o_srow, 2) ||
-      !aligned_ok(o, o_sb, o_sh, o_srow, 2) || !aligned_ok(dq, q_sb, q_sh, q_srow, 2))
-    return PCOPS_ERR_UNSUPPORTED;
-  const Strides st{PC_ATTN_STRIDE_ARGS, H};
+  if (Lk <= 0) return PCOPS_ERR_INVALID;
   ColPart cp;
+  AttnArgs a{PC_ATTN_ARGS};
+  a.o = o;
+  a.dout = dout;
+  a.lse = lse;
+  a.delta_out = (float *)workspace;
+  a.dq = dq;
+  a.cp = &cp;
+  rc = validate({{q, kAsQ}, {k, kAsK}, {v, kAsV}, {o, kAsO}, {dout, kAsO}, {lse, kPlain}, {dq, kAsQ}}, a.st, 2,
+                workspace, workspace_bytes, pcops_attention_bwd_colsum_workspace_bytes(B, H, Lq, Lk, D));
+  if (rc) return rc;
   cp.a = (float *)((char *)workspace + delta_bytes(B, H, Lq));
-  rc = dq2_dispatch(q, k, v, dout, lse, nullptr, dq, BH, Lq, Lk, D, scale, st, s, o, (float *)workspace, &cp);
+  rc = dq2_dispatch(a, D);
   if (rc) return rc;
   return launch_colsum_reduce(cp.a, dq_colsum, nullptr, nullptr, B * cp.nrb, H * D, s);
 }
@@ -2287,29 +2034,31 @@ extern "C" int pcops_attention_bwd_dkv_colsum(const void *q, const void *k, cons
   if (B < 0 || H <= 0) return PCOPS_ERR_INVALID;
   int rc = check_common(B * H, Lq, Lk, D, dtype);
   if (rc) return rc;
-  if (dtype != 1 || use_v1()) return PCOPS_ERR_UNSUPPORTED;
-  const int BH = B * H;
+  if (dtype != 1) return PCOPS_ERR_UNSUPPORTED;
   if (!dk_colsum || !dv_colsum) return PCOPS_ERR_INVALID;
   hipStream_t s = (hipStream_t)stream;
-  if (BH == 0) return PCOPS_OK;
+  if (B * H == 0) return PCOPS_OK;
   if (Lk == 0) {
     if (pc_memset_async(dk_colsum, 0, (size_t)H * D * sizeof(float), s) != hipSuccess ||
         pc_memset_async(dv_colsum, 0, (size_t)H * D * sizeof(float), s) != hipSuccess)
       return PCOPS_ERR_LAUNCH;
     return PCOPS_OK;
   }
-  if (!q || !k || !v || !dout || !lse || !dk || !dv || Lq <= 0) return PCOPS_ERR_INVALID;
-  if (!workspace || workspace_bytes < pcops_attention_bwd_colsum_workspace_bytes(B, H, Lq, Lk, D))
-    return PCOPS_ERR_WORKSPACE;
-  if (!aligned_ok(q, q_sb, q_sh, q_srow, 2) || !aligned_ok(k, k_sb, k_sh, k_srow, 2) ||
-      !aligned_ok(v, v_sb, v_sh, v_srow, 2) || !aligned_ok(dout, o_sb, o_sh, o_srow, 2) ||
-      !aligned_ok(dk, k_sb, k_sh, k_srow, 2) || !aligned_ok(dv, v_sb, v_sh, v_srow, 2))
-    return PCOPS_ERR_UNSUPPORTED;
-  const Strides st{PC_ATTN_STRIDE_ARGS, H};
+  if (Lq <= 0) return PCOPS_ERR_INVALID;
   ColPart cp;
+  AttnArgs a{PC_ATTN_ARGS};
+  a.dout = dout;
+  a.lse = lse;
+  a.delta = (const float *)workspace;
+  a.dk = dk;
+  a.dv = dv;
+  a.cp = &cp;
+  rc = validate({{q, kAsQ}, {k, kAsK}, {v, kAsV}, {dout, kAsO}, {lse, kPlain}, {dk, kAsK}, {dv, kAsV}}, a.st, 2,
+                workspace, workspace_bytes, pcops_attention_bwd_colsum_workspace_bytes(B, H, Lq, Lk, D));
+  if (rc) return rc;
   cp.a = (float *)((char *)workspace + delta_bytes(B, H, Lq));
-  cp.b = cp.a + (long long)BH * ((Lk + 127) / 128) * D;
-  rc = dkv2_dispatch(q, k, v, dout, lse, (const float *)workspace, dk, dv, BH, Lq, Lk, D, scale, st, s, &cp);
+  cp.b = cp.a + (long long)B * H * ((Lk + 127) / 128) * D;
+  rc = dkv2_dispatch(a, D);
   if (rc) return rc;
   return launch_colsum_reduce(cp.a, dk_colsum, cp.b, dv_colsum, B * cp.nrb, H * D, s);
 }
@@ -2333,7 +2082,9 @@ extern "C" int pcops_attention_backward(const void *q, const void *k, const void
 // The whole backward in one call (delta, dK/dV, dQ, and with *_colsum non-null the
 // in_proj bias column sums of all three).  bf16 with D >= 96: the dK/dV pass stores dS^T and
 // dQ = dS K is read back from it (attn_dqs_kernel: 1 GEMM unit instead of the 3 of the
-// recomputing pass; bitwise the same dQ); otherwise the two-pass sequence above.
+// recomputing pass; bitwise the same dQ); otherwise the two-pass sequence above.  This entry
+// always takes the dS^T form there -- it is what the entry is for; at hd 128, 2048^2 it measured
+// 2.59 ms against the two passes' 2.50 (profiles/r4_attn_ds_ab.txt), so callers opt in.
 extern "C" unsigned long long pcops_attention_bwd_fused_workspace_bytes(int B, int H, int Lq, int Lk, int D,
                                                                          int dtype) {
   if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || D <= 0) return 0;
@@ -2355,10 +2106,9 @@ extern "C" int pcops_attention_bwd_fused(const void *q, const void *k, const voi
   if (rc) return rc;
   const bool sums = dq_colsum || dk_colsum || dv_colsum;
   if (sums && !(dq_colsum && dk_colsum && dv_colsum)) return PCOPS_ERR_INVALID;
-  if (sums && (dtype != 1 || use_v1())) return PCOPS_ERR_UNSUPPORTED;
+  if (sums && dtype != 1) return PCOPS_ERR_UNSUPPORTED;
   if (workspace_bytes < pcops_attention_bwd_fused_workspace_bytes(B, H, Lq, Lk, D, dtype)) return PCOPS_ERR_WORKSPACE;
-  const bool ds = dtype == 1 && !use_v1() && D >= 96 && ds_path_on();
-  if (!ds) {
+  if (!(dtype == 1 && D >= 96)) {
     if (!sums)
       return pcops_attention_backward(q, k, v, o, dout, lse, dq, dk, dv, B, H, Lq, Lk, D, scale, dtype,
                                       PC_ATTN_STRIDE_ARGS, workspace, workspace_bytes, stream);
@@ -2382,31 +2132,33 @@ extern "C" int pcops_attention_bwd_fused(const void *q, const void *k, const voi
         if (pc_memset_async(p, 0, (size_t)H * D * sizeof(float), s) != hipSuccess) return PCOPS_ERR_LAUNCH;
     return PCOPS_OK;
   }
-  if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !workspace) return PCOPS_ERR_INVALID;
-  if (!aligned_ok(q, q_sb, q_sh, q_srow, 2) || !aligned_ok(k, k_sb, k_sh, k_srow, 2) ||
-      !aligned_ok(v, v_sb, v_sh, v_srow, 2) || !aligned_ok(dout, o_sb, o_sh, o_srow, 2) ||
-      !aligned_ok(o, o_sb, o_sh, o_srow, 2) || !aligned_ok(dq, q_sb, q_sh, q_srow, 2) ||
-      !aligned_ok(dk, k_sb, k_sh, k_srow, 2) || !aligned_ok(dv, v_sb, v_sh, v_srow, 2))
-    return PCOPS_ERR_UNSUPPORTED;
-  const Strides st{PC_ATTN_STRIDE_ARGS, H};
-  float *delta = (float *)workspace;
+  ColPart cpkv, cpq;
+  AttnArgs a{PC_ATTN_ARGS};
+  a.o = o;
+  a.dout = dout;
+  a.lse = lse;
+  a.delta = a.delta_out = (float *)workspace;
+  a.dq = dq;
+  a.dk = dk;
+  a.dv = dv;
+  a.cp = sums ? &cpkv : nullptr;
+  rc = validate({{q, kAsQ}, {k, kAsK}, {v, kAsV}, {o, kAsO}, {dout, kAsO}, {lse, kPlain}, {dq, kAsQ}, {dk, kAsK},
+                 {dv, kAsV}, {workspace, kPlain}},
+                a.st, 2);
+  if (rc) return rc;
   const long long rk = (Lk + 127) / 128, rq = (Lq + 127) / 128;
   float *parts = (float *)((char *)workspace + delta_bytes(B, H, Lq));
   __bf16 *dsT = (__bf16 *)((char *)parts + ((((unsigned long long)BH * (rq + 2 * rk) * D * sizeof(float)) + 255) &
                                             ~255ull));
-  ColPart cpkv, cpq;
   cpkv.a = parts;
   cpkv.b = parts + (long long)BH * rk * D;
   cpq.a = parts + 2ll * BH * rk * D;
-  ColPart *pkv = sums ? &cpkv : nullptr, *pq = sums ? &cpq : nullptr;
   switch (D) {
     case 96:
-      rc = sums ? launch_bwd_ds<96, true>(q, k, v, o, dout, lse, dq, dk, dv, BH, Lq, Lk, scale, st, s, delta, dsT, pq, pkv)
-                : launch_bwd_ds<96, false>(q, k, v, o, dout, lse, dq, dk, dv, BH, Lq, Lk, scale, st, s, delta, dsT, pq, pkv);
+      rc = sums ? launch_bwd_ds<96, true>(a, dsT, &cpq) : launch_bwd_ds<96, false>(a, dsT, nullptr);
       break;
     case 128:
-      rc = sums ? launch_bwd_ds<128, true>(q, k, v, o, dout, lse, dq, dk, dv, BH, Lq, Lk, scale, st, s, delta, dsT, pq, pkv)
-                : launch_bwd_ds<128, false>(q, k, v, o, dout, lse, dq, dk, dv, BH, Lq, Lk, scale, st, s, delta, dsT, pq, pkv);
+      rc = sums ? launch_bwd_ds<128, true>(a, dsT, &cpq) : launch_bwd_ds<128, false>(a, dsT, nullptr);
       break;
     default:
       return PCOPS_ERR_UNSUPPORTED;

@@ -1002,6 +1002,52 @@ def test_attention_bwd_fused_equals_two_pass(dev, monkeypatch, B, H, Lq, Lk, E, 
                 assert ((sa.double() - sb.double()).abs() <= bound).all(), (sa - sb).abs().max().item()
 
 
+def _one_head_backward(q, k, v, g, dq):
+    """pcops_attention_forward then pcops_attention_backward on one (L, D) head (B = H = 1), called
+    directly.  q and dq are (Lq, D) windows that share their row stride; k, v, g are contiguous."""
+    from svdformer_pointsea_amd import _lib
+    from svdformer_pointsea_amd._lib import lib, ptr, stream_of
+
+    (Lq, D), Lk = q.shape, k.shape[0]
+    assert q.stride() == dq.stride() and q.stride(1) == 1
+    o, dk, dv = torch.empty_like(g), torch.empty_like(k), torch.empty_like(v)
+    lse = torch.empty(1, Lq, dtype=torch.float32, device=q.device)
+    st = (D, D, q.stride(0), D, D, k.stride(0), D, D, v.stride(0), D, D, o.stride(0))
+    scale = 1.0 / math.sqrt(D)
+    _lib.call("attention forward", lib().pcops_attention_forward, ptr(q), ptr(k), ptr(v), ptr(o), ptr(lse), 1, 1,
+              Lq, Lk, D, scale, 1, *st, stream_of(q))
+    wsb = lib().pcops_attention_bwd_workspace_bytes(1, 1, Lq, Lk, D)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
+    _lib.call("attention bwd", lib().pcops_attention_backward, ptr(q), ptr(k), ptr(v), ptr(o), ptr(g), ptr(lse),
+              ptr(dq), ptr(dk), ptr(dv), 1, 1, Lq, Lk, D, scale, 1, *st, ptr(ws), wsb, stream_of(q))
+    torch.cuda.synchronize()
+    return dq, dk, dv
+
+
+@pytest.mark.parametrize("D", [96, 128])
+def test_attention_dkv_large_row_stride(dev, D):
+    """bf16 dK/dV at D >= 96 with a q / dq row stride of 2^25 elements: 64 rows span 2^31, beyond the
+    pipelined pass's 32-bit tile offsets, so the launcher falls back to the 8-wave split passes
+    (attn_dkv2_kernel MODE 1 + MODE 2), their only use.  The same values in contiguous tensors take
+    the pipelined pass; both orders of accumulation are the same, so dq, dk and dv are bitwise equal.
+    Lq = 70: one full and one partial 64-row query tile; Lk = 300: partial in the 128-key blocks of
+    the pipelined pass and in the 256-key blocks of the split ones."""
+    Lq, Lk, row = 70, 300, 1 << 25
+    gen = torch.Generator().manual_seed(300 + D)
+    q, k, v, g = [torch.randn(L, D, generator=gen).to(dev, torch.bfloat16) for L in (Lq, Lk, Lk, Lq)]
+    ref = _one_head_backward(q, k, v, g, torch.empty_like(q))
+    buf = torch.empty(Lq, row, dtype=torch.bfloat16, device=dev)  # 4.7 GB, uninitialised but for the windows
+    qs, dqs = buf[:, 0:D], buf[:, D:2 * D]
+    qs.copy_(q)
+    dqs.zero_()
+    got = _one_head_backward(qs, k, v, g, dqs)
+    for name, a, b in zip(("dq", "dk", "dv"), got, ref):
+        assert torch.isfinite(a.float()).all() and torch.isfinite(b.float()).all(), name
+        diff = (a.float() - b.float()).abs().max().item()
+        print(f"D={D} {name}: max |strided - contiguous| = {diff:.3e}, max |ref| = {b.float().abs().max().item():.3e}")
+        assert torch.equal(a, b), (name, diff)
+
+
 @pytest.mark.parametrize("B,N,H,sdt", [(2, 2048, 512, torch.float32), (3, 512, 768, torch.float32),
                                        (2, 1024, 256, torch.bfloat16), (1, 100, 64, torch.float32)])
 def test_add_posemb_kernel(dev, B, N, H, sdt):

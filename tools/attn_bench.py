@@ -1,9 +1,8 @@
 """Attention core timing at the PCN shapes (B=32), forward and backward,
-per libpcops launch (HIP events via _lib.KernelTimer).  PCOPS_ATTN_V1=1 in
-the environment selects the first-generation kernels for A/B runs; PCOPS_ATTN_FUSED=0
-the two-pass backward for head_dim >= 96 ("bwd" = the one-call backward, credited
-10*BH*Lq*Lk*D).  ATTN_BENCH_SUMS=1: the step's form -- q / k / v as windows of one packed
-(L, B, 3E) source whose gradient feeds a biased Linear, so the backward passes also form the
+per libpcops launch (HIP events via _lib.KernelTimer).  PCOPS_LIB_PATH selects the
+library build (A/B runs: tools/gpu_run.sh attn_lib_ab); PCOPS_ATTN_FUSED=1 the one-call
+backward for head_dim >= 96 ("bwd", credited 10*BH*Lq*Lk*D).  ATTN_BENCH_SUMS=1: the
+step's form -- q / k / v as windows of one packed (L, B, 3E) source whose gradient feeds a biased Linear, so the backward passes also form the
 in_proj bias column sums (the *_colsum kernels)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,7 +15,7 @@ B = 32
 shapes = [  # (Lq, Lk, E, H) seen in the PCN step
     (2048, 2048, 512, 8), (2048, 2048, 1024, 8), (2048, 512, 512, 8), (512, 512, 768, 8), (512, 512, 512, 8),
     (128, 128, 512, 4)]
-tag = os.environ.get("PCOPS_LIB_PATH", "v1" if os.environ.get("PCOPS_ATTN_V1") == "1" else "v2")
+tag = os.environ.get("PCOPS_LIB_PATH", "v2")
 sel = [int(a) for a in sys.argv[1:]]
 for si, (Lq, Lk, E, H) in enumerate(shapes):
     if sel and si not in sel:

@@ -1,8 +1,8 @@
-"""A/B correctness of attention kernel variants selected by environment switches
-(read once per process, so each variant runs in its own process):
+"""A/B correctness of two builds of the library (the base one loaded through
+PCOPS_LIB_PATH; tools/gpu_run.sh attn_lib_ab runs the three steps):
 
-  PCOPS_DKV3=1 python tools/attn_variant.py dump out_b.pt
-  python tools/attn_variant.py dump out_a.pt
+  PCOPS_LIB_PATH=base/libpcops.so python tools/attn_variant.py dump out_a.pt
+  python tools/attn_variant.py dump out_b.pt
   python tools/attn_variant.py cmp out_a.pt out_b.pt
 
 dump: bf16 forward + backward of the attention core at the PCN shapes (B = 2)

@@ -15,7 +15,7 @@
 #   dist1        bench.py under torch.distributed.run with ONE rank and an RCCL group
 #                (--dist-selftest): the bucketed all-reduce captured in the graph
 #   step_profile tools/step_profile.py (torch-profiler op/kernel breakdown of one eager step)
-#   attn_ab      tools/attn_bench.py once per env group in $ATTN_AB (A/B of attention variants)
+#   attn_lib_ab  attention A/B of two library builds: $AB_BASE (a .so) against the in-tree one
 #   avail        rocprofv3 --list-avail
 #   knn          tools/knn_bench.py ; chamfer: tools/microbench.py chamfer
 set -o pipefail
@@ -131,12 +131,6 @@ run_stage() {
         python tools/attn_bench.py 0 1 > "$OUT/pmc_attn2.log" 2>&1 &&
       python tools/pmc_summary.py "$(find "$OUT/pmc_attn2" -name '*counter_collection.csv' -print -quit)" \
         > "$OUT/pmc_attn2_summary.txt" ;;
-    attn_ab)   # A/B of attention variants selected by env (ATTN_AB="VAR=a VAR=b;VAR=c" groups)
-      IFS=';' read -ra groups <<< "${ATTN_AB:-PCOPS_FWD_PIPE=0}"
-      for g in "${groups[@]}"; do
-        echo "== $g" >> "$OUT/attn_ab.txt"
-        env $g timeout -k 10 120 python tools/attn_bench.py ${ATTN_SHAPES:-0 1 2 3} >> "$OUT/attn_ab.txt" 2>&1 || return 1
-      done ;;
     step_profile) timeout -k 10 400 python tools/step_profile.py --rows 60 > "$OUT/step_ops.txt" 2>&1 ;;
     gemm_table) GEMM_TABLE=1 timeout -k 10 400 python tools/op_shapes.py x 60 > "$OUT/gemm_table.txt" 2>&1 ;;
     op_shapes) timeout -k 10 400 python tools/op_shapes.py "${OPS_RE:-^aten::(copy_|cat|fill_|_to_copy)$}" 60 \
@@ -158,15 +152,6 @@ run_stage() {
         echo "== $g" >> "$OUT/fps_bench.txt"
         env $g timeout -k 10 120 python tools/fps_bench.py >> "$OUT/fps_bench.txt" 2>&1 || return 1
       done ;;
-    attn_var)  # bitwise / float64 check of an attention variant: default vs each env group in $ATTN_VAR
-      timeout -k 10 300 python tools/attn_variant.py dump "$OUT/attn_var_base.pt" > "$OUT/attn_var.txt" 2>&1 || return 1
-      IFS=';' read -ra groups <<< "${ATTN_VAR:?set ATTN_VAR}"
-      for g in "${groups[@]}"; do
-        echo "== $g" >> "$OUT/attn_var.txt"
-        env $g timeout -k 10 300 python tools/attn_variant.py dump "$OUT/attn_var_x.pt" >> "$OUT/attn_var.txt" 2>&1 || return 1
-        python tools/attn_variant.py cmp "$OUT/attn_var_base.pt" "$OUT/attn_var_x.pt" >> "$OUT/attn_var.txt" 2>&1
-      done
-      rm -f "$OUT"/attn_var_*.pt ;;
     attn_det) timeout -k 10 300 python tools/attn_determinism.py > "$OUT/attn_det.txt" 2>&1 ;;
     attn_err) timeout -k 10 300 python tools/attn_err.py > "$OUT/attn_err.jsonl" 2>&1 ;;
     chamfer) timeout -k 10 120 python tools/microbench.py > "$OUT/chamfer_bench.txt" 2>&1 ;;

@@ -148,6 +148,42 @@ int pcops_three_interpolate(const float *points, const int *idx, const float *we
 int pcops_three_interpolate_grad(const float *grad_out, const int *idx, const float *weight, int B, int C, int N,
                                  int M, float *grad_points, pcops_stream_t stream);
 
+/* ---------------- PointNet++ SA / FP composites ----------------
+ * pcops_ball_group: sample_and_group (models/model_utils.py:117-128) and QueryAndGroup
+ * (pointnet2_utils.py:298-346) after the FPS gather, i.e. ball_query (ball_query_gpu.cu:9-44) and
+ * the grouping / centring / concat / layout copy, in one launch.  xyz (B,N,3), new_xyz (B,S,3),
+ * points_t (B,N,C) token-major (NULL when C == 0) ->
+ *   idx (B,S,K) int32: the first K points with sqd3(new - p) < radius * radius in index order,
+ *     the slots after the last hit holding the first hit, a centre without a hit holding zeros
+ *     (bit-equal to pcops_ball_query);
+ *   out (B,S,K,3+C) row-major, out_dtype 0 = fp32 / 1 = bf16 rounded once: pcops_sa_group's rows
+ *     for that idx (index rule above: with N == 0 index 0 reads zero, xyz / points_t may be NULL).
+ * One wave per centre, 64 candidates per step; deterministic.  0 <= K <= 1024, a larger K returns
+ * PCOPS_ERR_INVALID (callers then run pcops_ball_query + pcops_sa_group).  The gradient is
+ * pcops_sa_group_grad with the emitted idx. */
+int pcops_ball_group(const float *xyz, const float *new_xyz, const float *points_t, int B, int N, int S, int K, int C,
+                     float radius, int *idx, void *out, int out_dtype, pcops_stream_t stream);
+/* pcops_fp_interp_forward: PointNet_FP_Module.forward (models/model_utils.py:243-253) and
+ * PointnetFPModule.forward (pointnet2_modules.py:185-204) up to the MLP: three_nn, the
+ * inverse-distance weights, three_interpolate and the concat with the skip features, token-major.
+ * unknown (B,N,3), known (B,M,3), points2_t (B,M,C2), points1_t (B,N,C1) or NULL (C1 == 0) ->
+ *   idx (B,N,3) int32: bit-equal to pcops_three_nn (for M < 3 the unfilled slots keep index 0);
+ *   weight (B,N,3) fp32: with d = sqrt(dist2), r = 1 / max(d, 1e-10) (mode 0, model_utils.py:244-247)
+ *     or r = 1 / (d + 1e-8) (mode 1, pointnet2_modules.py:187-189), w = r / (r0 + r1 + r2); an
+ *     unfilled (inf) slot gets exactly 0;
+ *   out (B,N,C2+C1), out_dtype 0 / 1: out[..,c<C2] = fma(p2,w2, fma(p0,w0, p1*w1)) of the three
+ *     points2_t rows (pcops_three_interpolate's order), out[..,C2+c] = points1_t[..,c].
+ * M >= 1 (M == 0 returns PCOPS_ERR_INVALID), B <= 65535.
+ * pcops_fp_interp_backward: three_interpolate_grad (interpolate_gpu.cu:116-154) token-major:
+ * grad_points2_t (B,M,C2) fp32, overwritten, += g[b,j,c] * weight[b,j,r] at idx[b,j,r] over the
+ * leading C2 columns of grad_out (B,N,Ct), grad_dtype 0 / 1.  The skip gradient is the trailing
+ * column slice of grad_out; coordinates get no gradient (pointnet2_utils.py:124-127). */
+int pcops_fp_interp_forward(const float *unknown, const float *known, const float *points2_t, const float *points1_t,
+                            int B, int N, int M, int C2, int C1, int mode, int *idx, float *weight, void *out,
+                            int out_dtype, pcops_stream_t stream);
+int pcops_fp_interp_backward(const void *grad_out, int grad_dtype, const int *idx, const float *weight, int B, int N,
+                             int M, int C2, int Ct, float *grad_points2_t, pcops_stream_t stream);
+
 /* ---------------- kNN (models/model_utils.py:258-286, :807-845) ----------------
  * query_knn / query_knn_point: K nearest points of p for every query q, in
  * ascending (squared distance, index) order; distance evaluated exactly as

@@ -3,7 +3,8 @@ SVDFormer / PointSea per-batch completion hot path.
 
 Drop-in modules mirroring the reference's operator API:
   svdformer_pointsea_amd.pointnet2_utils  <- pointnet2_ops.pointnet2_utils
-  svdformer_pointsea_amd.chamfer3D        <- metrics.CD.chamfer3D.dist_chamfer_3D
+  svdformer_pointsea_amd.pointnet2_modules <- pointnet2_ops.pointnet2_modules
+  svdformer_pointsea_amd.chamfer3D      <- metrics.CD.chamfer3D.dist_chamfer_3D
   svdformer_pointsea_amd.emd_module       <- metrics.EMD.emd_module
   svdformer_pointsea_amd.model_utils      <- models/model_utils.py hot-path pieces
   svdformer_pointsea_amd.attention        <- self/cross_attention, SDG_Decoder (model_utils.py)

@@ -40,6 +40,9 @@ _SIGS = {
     "pcops_three_nn": (I, [P, P, I, I, I, P, P, P]),
     "pcops_three_interpolate": (I, [P, P, P, I, I, I, I, P, P]),
     "pcops_three_interpolate_grad": (I, [P, P, P, I, I, I, I, P, P]),
+    "pcops_ball_group": (I, [P, P, P, I, I, I, I, I, F, P, P, I, P]),
+    "pcops_fp_interp_forward": (I, [P, P, P, P, I, I, I, I, I, I, P, P, P, I, P]),
+    "pcops_fp_interp_backward": (I, [P, I, P, P, I, I, I, I, I, P, P]),
     "pcops_knn": (I, [P, P, I, I, I, I, I, I, P, P, P]),
     "pcops_knn_workspace_bytes": (ULL, [I, I, I, I, I]),
     "pcops_knn_ws": (I, [P, P, I, I, I, I, I, I, P, P, P, ULL, P]),

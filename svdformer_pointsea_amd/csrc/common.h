@@ -23,6 +23,23 @@ __device__ __forceinline__ f32x2 sqd3_pk(f32x2 a, f32x2 b, f32x2 c) {
   return __builtin_elementwise_fma(c, c, __builtin_elementwise_fma(a, a, b * b));
 }
 
+// three_nn's compare chain (interpolate_gpu.cu:32-47): candidate k at squared distance d enters
+// the ascending (best1, best2, best3) list by strict '<', so the lower index wins a tie.  Shared
+// by three_nn_kernel and fp_interp_kernel, whose idx / dist2 are therefore the same bits.
+__device__ __forceinline__ void nn3_insert(float d, int k, float &best1, float &best2, float &best3, int &bi1,
+                                           int &bi2, int &bi3) {
+  if (d < best1) {
+    best3 = best2; bi3 = bi2;
+    best2 = best1; bi2 = bi1;
+    best1 = d; bi1 = k;
+  } else if (d < best2) {
+    best3 = best2; bi3 = bi2;
+    best2 = d; bi2 = k;
+  } else if (d < best3) {
+    best3 = d; bi3 = k;
+  }
+}
+
 __device__ __forceinline__ int lane_id() { return __lane_id(); }
 
 // ---- wave-level reductions (DPP / swizzle lowered by the compiler) ----

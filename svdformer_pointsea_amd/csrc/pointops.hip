@@ -82,18 +82,7 @@ __global__ void three_nn_kernel(const float *__restrict__ unknown, const float *
     __syncthreads();
     for (int e = 0; e < cnt; ++e) {
       const float4 c = kt[e];
-      const float d = sqd3(ux - c.x, uy - c.y, uz - c.z);
-      const int k = t0 + e;
-      if (d < best1) {
-        best3 = best2; bi3 = bi2;
-        best2 = best1; bi2 = bi1;
-        best1 = d; bi1 = k;
-      } else if (d < best2) {
-        best3 = best2; bi3 = bi2;
-        best2 = d; bi2 = k;
-      } else if (d < best3) {
-        best3 = d; bi3 = k;
-      }
+      nn3_insert(sqd3(ux - c.x, uy - c.y, uz - c.z), t0 + e, best1, best2, best3, bi1, bi2, bi3);
     }
     __syncthreads();
   }

@@ -10,6 +10,9 @@ its model classes can import them unchanged:
   sample_and_group_knn(xyz, points, npoint, k, ...)     :323-356
   sample_and_group_knn_cl (fused grouping, channels_last) :323-356 + the first conv's layout
   edge_features (EdgeConv's [x_i - x_j, x_i], channels_last) :812-845, 869-877
+  Conv1d / sample_and_group / PointNet_SA_Module / PointNet_FP_Module   :9-25, 97-256
+  ball_group_cl (fused ball query + grouping, channels_last) :97-130 + the first conv's layout
+  fp_interp_cl (fused three-NN + weights + interpolation + skip concat, token-major) :243-253
   self_attention / cross_attention / SDG_Decoder        :542-629
   self_attention_woinp / SDG_Decoder_PointSea           models_PointSea/model_utils.py:463-509
   PCViews                                               :1179-1234
@@ -242,3 +245,311 @@ def edge_features(x, k, out_dtype=None):
     pts = x.float().transpose(1, 2).contiguous()   # (B, N, C) fp32: the kNN's operand and the gather source
     idx = _knn(pts.detach(), pts.detach(), k)
     return _EdgeGroup.apply(pts, idx, out_dtype).permute(0, 3, 1, 2)
+
+
+# ------------------------------------------------------------------ PointNet++ SA / FP (radius path)
+# PCOPS_PN2_FUSED=0: the SA / FP modules run the unfused chain of the existing ops (ball_query,
+# grouping_operation, three_nn, three_interpolate, torch glue) -- A/B runs and the parity tests
+_PN2_FUSED = os.environ.get("PCOPS_PN2_FUSED", "1") != "0"
+BALL_GROUP_MAX_K = 1024   # pcops_ball_group's index slots per wave
+
+
+def _cm(a, a_t):
+    """The channel-major (B,C,N) form of a tensor given channel-major or token-major (or neither)."""
+    return a if a is not None else (None if a_t is None else a_t.transpose(1, 2))
+
+
+def _rows_dtype():
+    return torch.bfloat16 if torch.is_autocast_enabled("cuda") else torch.float32
+
+
+class _BallGroup(torch.autograd.Function):
+    """pcops_ball_group: ball query and the grouped (xyz - centre, points) rows in one launch."""
+
+    @staticmethod
+    def forward(ctx, xyz_t, new_xyz_t, points_t, radius, K, out_dtype):
+        B, N, _ = xyz_t.shape
+        S = new_xyz_t.shape[1]
+        C = 0 if points_t is None else points_t.shape[2]
+        out = torch.empty(B, S, K, 3 + C, dtype=out_dtype, device=xyz_t.device)
+        idx = torch.empty(B, S, K, dtype=torch.int32, device=xyz_t.device)
+        with torch.cuda.device(xyz_t.device):
+            call("ball_group", lib().pcops_ball_group, ptr(xyz_t), ptr(new_xyz_t), ptr(points_t), B, N, S, K, C,
+                 float(radius), ptr(idx), ptr(out), 1 if out_dtype == torch.bfloat16 else 0, stream_of(xyz_t))
+        ctx.save_for_backward(idx)
+        ctx.dims = (B, N, S, K, C)
+        ctx.mark_non_differentiable(idx)
+        return out, idx
+
+    @staticmethod
+    def backward(ctx, g, _gidx):
+        (idx,) = ctx.saved_tensors
+        B, N, S, K, C = ctx.dims
+        if C == 0 or not ctx.needs_input_grad[2]:
+            return None, None, None, None, None, None
+        g = g.contiguous()
+        gp = torch.empty(B, N, C, dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            call("sa_group_grad", lib().pcops_sa_group_grad, ptr(g), 1 if g.dtype == torch.bfloat16 else 0, ptr(idx),
+                 B, N, S, K, C, ptr(gp), stream_of(g))
+        return None, None, gp, None, None, None
+
+
+def ball_group_rows(xyz_t, new_xyz_t, points_t, radius, nsample, out_dtype=torch.float32):
+    """Ball query around new_xyz_t (B,S,3) in xyz_t (B,N,3) and the grouped rows
+    [xyz[idx] - centre, points_t[idx]] -> rows (B,S,K,3+C) in out_dtype, idx (B,S,K) int32: ONE
+    launch (pcops_ball_group); an nsample beyond BALL_GROUP_MAX_K runs ball_query + pcops_sa_group,
+    the same rows.  Coordinates carry no gradient (as sample_and_group_knn_cl); points_t does."""
+    from .pointnet2_utils import ball_query
+
+    xyz_t = xyz_t.detach().float().contiguous()
+    new_xyz_t = new_xyz_t.detach().float().contiguous()
+    require_float(xyz_t, "xyz")
+    require_float(new_xyz_t, "new_xyz")
+    if points_t is not None:
+        points_t = points_t.float().contiguous()
+    nsample = int(nsample)
+    if nsample > BALL_GROUP_MAX_K:
+        idx = ball_query(radius, nsample, xyz_t, new_xyz_t)
+        return _SAGroup.apply(xyz_t, new_xyz_t, points_t, idx, out_dtype), idx
+    return _BallGroup.apply(xyz_t, new_xyz_t, points_t, radius, nsample, out_dtype)
+
+
+def ball_group_cl(xyz, points_t, npoint, nsample, radius, out_dtype=torch.float32, fidx=None):
+    """sample_and_group (model_utils.py:97-130, use_xyz) in two launches after the FPS gather's --
+    FPS, gather, and ONE pcops_ball_group that searches the ball and writes the neighbourhood rows
+    into the channels_last memory the first 1x1 conv reads.  xyz (B,3,N) without gradient,
+    points_t (B,N,C) token-major (or None) -> new_xyz (B,3,S), features (B,3+C,S,K) channels_last,
+    idx (B,S,K).  The radius twin of sample_and_group_knn_cl."""
+    xyz_t = xyz.transpose(1, 2).contiguous()
+    fidx = furthest_point_sample(xyz_t, npoint) if fidx is None else fidx.take(npoint)
+    new_xyz = gather_operation(xyz.contiguous(), fidx)                 # (B,3,S), the reference's new_xyz
+    rows, idx = ball_group_rows(xyz_t, new_xyz.transpose(1, 2), points_t, radius, nsample, out_dtype)
+    return new_xyz, rows.permute(0, 3, 1, 2), idx
+
+
+def sample_and_group(xyz, points, npoint, nsample, radius, use_xyz=True):
+    """model_utils.py:97-130: FPS -> gather -> ball query -> group (xyz, points); the unfused chain.
+    xyz (B,3,N), points (B,f,N) -> new_xyz (B,3,npoint), new_points (B, 3 | f+3 | f, npoint, nsample),
+    idx (B,npoint,nsample), grouped_xyz (B,3,npoint,nsample)."""
+    from .pointnet2_utils import ball_query
+
+    xyz_flipped = xyz.permute(0, 2, 1).contiguous()
+    new_xyz = gather_operation(xyz, furthest_point_sample(xyz_flipped, npoint))
+    idx = ball_query(radius, nsample, xyz_flipped, new_xyz.permute(0, 2, 1).contiguous())
+    grouped_xyz = grouping_operation(xyz, idx)
+    grouped_xyz -= new_xyz.unsqueeze(3).repeat(1, 1, 1, nsample)
+    if points is not None:
+        grouped_points = grouping_operation(points, idx)
+        new_points = torch.cat([grouped_xyz, grouped_points], 1) if use_xyz else grouped_points
+    else:
+        new_points = grouped_xyz
+    return new_xyz, new_points, idx, grouped_xyz
+
+
+class _FPInterp(torch.autograd.Function):
+    """pcops_fp_interp_forward / _backward: three-NN, weights, interpolation and the skip concat."""
+
+    @staticmethod
+    def forward(ctx, unknown_t, known_t, points2_t, points1_t, mode, out_dtype):
+        B, N, _ = unknown_t.shape
+        M, C2 = known_t.shape[1], points2_t.shape[2]
+        C1 = 0 if points1_t is None else points1_t.shape[2]
+        dev = unknown_t.device
+        out = torch.empty(B, N, C2 + C1, dtype=out_dtype, device=dev)
+        idx = torch.empty(B, N, 3, dtype=torch.int32, device=dev)
+        weight = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            call("fp_interp_forward", lib().pcops_fp_interp_forward, ptr(unknown_t), ptr(known_t), ptr(points2_t),
+                 ptr(points1_t), B, N, M, C2, C1, int(mode), ptr(idx), ptr(weight), ptr(out),
+                 1 if out_dtype == torch.bfloat16 else 0, stream_of(unknown_t))
+        ctx.save_for_backward(idx, weight)
+        ctx.dims = (B, N, M, C2, C1)
+        ctx.mark_non_differentiable(idx, weight)
+        return out, idx, weight
+
+    @staticmethod
+    def backward(ctx, g, _gidx, _gweight):
+        idx, weight = ctx.saved_tensors
+        B, N, M, C2, C1 = ctx.dims
+        g = g.contiguous()
+        gp2 = gp1 = None
+        if ctx.needs_input_grad[2]:
+            gp2 = torch.empty(B, M, C2, dtype=torch.float32, device=g.device)
+            with torch.cuda.device(g.device):
+                call("fp_interp_backward", lib().pcops_fp_interp_backward, ptr(g), 1 if g.dtype == torch.bfloat16 else 0,
+                     ptr(idx), ptr(weight), B, N, M, C2, C2 + C1, ptr(gp2), stream_of(g))
+        if C1 and ctx.needs_input_grad[3]:
+            gp1 = g[..., C2:].float()   # the skip gradient: the trailing column slice
+        return None, None, gp2, gp1, None, None
+
+
+def fp_interp_cl(unknown_t, known_t, points1_t, points2_t, mode=0, out_dtype=torch.float32, return_weights=False):
+    """Feature propagation up to the MLP in ONE launch (pcops_fp_interp_forward): the three nearest
+    known points of every unknown point, the inverse-distance weights (mode 0: model_utils.py:244-247,
+    mode 1: pointnet2_modules.py:187-189), the interpolated points2_t rows and the skip features
+    points1_t, token-major.  unknown_t (B,N,3), known_t (B,M,3) without gradient, points2_t (B,M,C2),
+    points1_t (B,N,C1) or None -> (B,N,C2+C1) in out_dtype (with return_weights: also idx, weight)."""
+    unknown_t = unknown_t.detach().float().contiguous()
+    known_t = known_t.detach().float().contiguous()
+    require_float(unknown_t, "unknowns")
+    require_float(known_t, "knows")
+    points2_t = points2_t.float().contiguous()
+    if points1_t is not None:
+        points1_t = points1_t.float().contiguous()
+    out, idx, weight = _FPInterp.apply(unknown_t, known_t, points2_t, points1_t, mode, out_dtype)
+    return (out, idx, weight) if return_weights else out
+
+
+def fp_interp_chain(unknown_t, known_t, points1, points2, mode=0):
+    """The same rows by the existing ops: three_nn, the weight arithmetic in torch, three_interpolate,
+    torch.cat and the token-major copy.  points1 (B,C1,N) or None, points2 (B,C2,M) channel-major."""
+    from .pointnet2_utils import three_interpolate, three_nn
+
+    dist, idx = three_nn(unknown_t.contiguous(), known_t.contiguous())
+    if mode == 0:
+        recip = 1.0 / torch.clamp_min(dist, 1e-10)
+        weight = recip / torch.sum(recip, 2, keepdim=True).repeat((1, 1, 3))
+    else:
+        recip = 1.0 / (dist + 1e-8)
+        weight = recip / torch.sum(recip, dim=2, keepdim=True)
+    new_points = three_interpolate(points2.contiguous(), idx, weight)
+    if points1 is not None:
+        new_points = torch.cat([new_points, points1], 1)
+    return new_points.transpose(1, 2).contiguous()
+
+
+def _fp_fused(unknown_t, known_t):
+    return (_PN2_FUSED and unknown_t.is_cuda and not unknown_t.requires_grad and known_t is not None
+            and not known_t.requires_grad and known_t.shape[1] >= 1)
+
+
+class Conv1d(nn.Module):
+    """model_utils.py:9-25: Conv1d -> BatchNorm1d -> activation on (B,C,N).  forward_tokens runs the
+    same layer on token-major (B,N,C) rows: the kernel-size-1 conv as a GEMM, the BatchNorm over the
+    (B*N, C) rows; forward is forward_tokens between two transposes."""
+
+    def __init__(self, in_channel, out_channel, kernel_size=1, stride=1, if_bn=True, activation_fn=torch.relu):
+        super().__init__()
+        self.conv = nn.Conv1d(in_channel, out_channel, kernel_size, stride=stride)
+        self.if_bn = if_bn
+        self.bn = nn.BatchNorm1d(out_channel)
+        self.activation_fn = activation_fn
+
+    def _pointwise(self):
+        return self.conv.kernel_size == (1,) and self.conv.stride == (1,)
+
+    def forward_tokens(self, x):
+        from .attention import linear
+
+        if not self._pointwise():
+            return self.forward(x.transpose(1, 2)).transpose(1, 2)
+        out = linear(x, self.conv.weight.view(self.conv.out_channels, -1), self.conv.bias)
+        if self.if_bn:
+            out = self.bn(out.reshape(-1, out.shape[-1])).view(out.shape)
+        if self.activation_fn is not None:
+            out = self.activation_fn(out)
+        return out
+
+    def forward(self, x):
+        if self._pointwise():
+            return self.forward_tokens(x.transpose(1, 2)).transpose(1, 2)
+        out = self.conv(x)
+        if self.if_bn:
+            out = self.bn(out)
+        if self.activation_fn is not None:
+            out = self.activation_fn(out)
+        return out
+
+
+class PointNet_SA_Module(nn.Module):
+    """model_utils.py:161-207: FPS -> ball query -> group -> shared MLP -> max over the ball.
+    forward keeps the reference's layouts; forward_tokens takes and returns token-major tensors
+    (xyz_t (B,N,3), points_t (B,N,f) -> new_xyz_t (B,S,3), features (B,S,mlp[-1])).  On the GPU,
+    with use_xyz and coordinates that need no gradient, the grouping is one pcops_ball_group launch
+    (ball_group_cl); PCOPS_PN2_FUSED=0, or any other case, runs sample_and_group.  Both feed the
+    same MLP and max code."""
+
+    def __init__(self, npoint, nsample, radius, in_channel, mlp, if_bn=True, group_all=False, use_xyz=True):
+        super().__init__()
+        from .svdformer import Conv2d
+
+        self.npoint, self.nsample, self.radius, self.mlp = npoint, nsample, radius, mlp
+        self.group_all, self.use_xyz = group_all, use_xyz
+        if use_xyz:
+            in_channel += 3
+        last = in_channel
+        convs = []
+        for out_channel in mlp:
+            convs.append(Conv2d(last, out_channel, if_bn=if_bn))
+            last = out_channel
+        self.mlp_conv = nn.Sequential(*convs)
+
+    def _run(self, xyz, xyz_t, points, points_t):
+        from .svdformer import max_over_neighbours_tokens, sample_and_group_all
+
+        xyz = _cm(xyz, xyz_t)
+        if self.group_all:
+            new_xyz, new_points, _, _ = sample_and_group_all(xyz, _cm(points, points_t), self.use_xyz)
+        elif _PN2_FUSED and self.use_xyz and xyz.is_cuda and not xyz.requires_grad:
+            if points_t is None and points is not None:
+                points_t = points.transpose(1, 2)
+            new_xyz, new_points, _ = ball_group_cl(xyz, points_t, self.npoint, self.nsample, self.radius,
+                                                   _rows_dtype())
+        else:
+            points = _cm(points, points_t)
+            new_xyz, new_points, _, _ = sample_and_group(xyz.contiguous(), None if points is None else points.contiguous(),
+                                                         self.npoint, self.nsample, self.radius, self.use_xyz)
+        new_points = self.mlp_conv(new_points.contiguous(memory_format=torch.channels_last))
+        return new_xyz, max_over_neighbours_tokens(new_points)
+
+    def forward(self, xyz, points):
+        """xyz (B,3,N), points (B,f,N) -> new_xyz (B,3,npoint), new_points (B,mlp[-1],npoint)."""
+        new_xyz, tok = self._run(xyz, None, points, None)
+        return new_xyz, tok.transpose(1, 2).contiguous()
+
+    def forward_tokens(self, xyz_t, points_t):
+        new_xyz, tok = self._run(None, xyz_t, None, points_t)
+        return new_xyz.transpose(1, 2).contiguous(), tok
+
+
+class PointNet_FP_Module(nn.Module):
+    """model_utils.py:209-256: three-NN inverse-distance interpolation of points2 onto xyz1, concat
+    with points1, shared MLP.  forward keeps the reference's (B,C,N) layouts; forward_tokens takes
+    xyz1_t (B,N,3), xyz2_t (B,M,3), points1_t (B,N,C1), points2_t (B,M,C2) and returns (B,N,mlp[-1]).
+    On the GPU the interpolation and the concat are one pcops_fp_interp_forward launch
+    (fp_interp_cl); PCOPS_PN2_FUSED=0, or coordinates that need a gradient, run fp_interp_chain."""
+
+    def __init__(self, in_channel, mlp, use_points1=False, in_channel_points1=None, if_bn=True):
+        super().__init__()
+        self.use_points1 = use_points1
+        if use_points1:
+            in_channel += in_channel_points1
+        last = in_channel
+        convs = []
+        for out_channel in mlp:
+            convs.append(Conv1d(last, out_channel, if_bn=if_bn))
+            last = out_channel
+        self.mlp_conv = nn.Sequential(*convs)
+
+    def _run(self, xyz1_t, xyz2_t, points1, points1_t, points2, points2_t):
+        if not self.use_points1:
+            points1 = points1_t = None
+        if _fp_fused(xyz1_t, xyz2_t):
+            p1 = points1_t if points1_t is not None or points1 is None else points1.transpose(1, 2)
+            p2 = points2_t if points2_t is not None else points2.transpose(1, 2)
+            tok = fp_interp_cl(xyz1_t, xyz2_t, p1, p2, 0, _rows_dtype())
+        else:
+            tok = fp_interp_chain(xyz1_t, xyz2_t, _cm(points1, points1_t), _cm(points2, points2_t), 0)
+        for layer in self.mlp_conv:
+            tok = layer.forward_tokens(tok)
+        return tok
+
+    def forward(self, xyz1, xyz2, points1, points2):
+        """xyz1 (B,3,N), xyz2 (B,3,M), points1 (B,C1,N), points2 (B,C2,M) -> (B,mlp[-1],N)."""
+        tok = self._run(xyz1.permute(0, 2, 1).contiguous(), xyz2.permute(0, 2, 1).contiguous(), points1, None,
+                        points2, None)
+        return tok.transpose(1, 2).contiguous()
+
+    def forward_tokens(self, xyz1_t, xyz2_t, points1_t, points2_t):
+        return self._run(xyz1_t, xyz2_t, None, points1_t, None, points2_t)

@@ -686,6 +686,60 @@ int pcops_grid2image(const float *grid, const float *kern, int BV, int D, int R,
                      unsigned long long workspace_bytes, pcops_stream_t stream);
 unsigned long long pcops_grid2image_workspace_bytes(int BV, int D, int R);
 
+/* ---------------- view-space ops (models/model_utils.py:1004-1234) ----------------
+ * The gradient of pcops_points2depth with respect to the points (the autograd of
+ * PCViews.get_img :1196-1220 through points2depth :1111 and distribute :1053-1077).  img is
+ * the forward's output and wsum the float image the forward leaves in its workspace (the
+ * per-pixel weight sum, 0 on empty pixels), both (B*V, H, W); grad_img likewise.  The pixel of
+ * each (point, view) pair is recomputed by the forward's own code.  Only the depth carries a
+ * gradient (the pixel coordinates pass through ceil): with z the transformed depth,
+ * w = 1/(z + 1e-12) and Sw the pixel's weight sum after the "+1 where 0" rule (:1070-1071),
+ *   dz = g[pix] w^2 (1e-12 + img[pix]) / Sw[pix]   for a pair the splat keeps, else 0
+ *   grad_points[b,i,:] = sum over v, ascending, of dz_v rot[v][:, 2]
+ * A gather without atomics: every row of grad_points (B, N, 3) is stored exactly once, rows
+ * rejected in every view as exact zeros, and the result is bitwise reproducible. */
+int pcops_points2depth_backward(const float *points, const float *rot, const float *trans, const float *img,
+                                const float *wsum, const float *grad_img, int B, int N, int V, int H, int W,
+                                float *grad_points, pcops_stream_t stream);
+/* The pixel ex*W + ey that pcops_points2depth adds each (point, view) pair to (distribute
+ * :1025-1048 and :1060 with size 1), or -1 where it rejects the pair (the mask :1037-1041: off
+ * canvas, or depth < 0): pixel (B*V, N) int64, image r = b*V + v. */
+int pcops_points2pixel(const float *points, const float *rot, const float *trans, int B, int N, int V, int H, int W,
+                       long long *pixel, pcops_stream_t stream);
+
+/* Point <-> pixel feature exchange.  coord (B, N) holds one pixel coordinate per point, of
+ * dtype PCOPS_COORD_*.  Index rule (both calls): a coordinate c takes part iff
+ * 0 <= c <= P-1, tested on the stored value before any conversion, and its pixel is the
+ * truncation of c; any other value (negative, >= P, NaN, +-inf, beyond the int range)
+ * contributes nothing, reads as 0 and is never used as an address.  fp32 features.
+ * The image side is addressed as base[b*stride_b + p*stride_p + c*stride_c] (strides in
+ * elements): (B, P, C) rows are (P*C, C, 1), an NCHW map is (C*P, 1, P), a channels_last map
+ * is (P*C, C, 1) -- no layout copy on either side.
+ *
+ * pcops_pixel_gather -- distribute_img_fea_points (:1157-1176, batched_index_select
+ * :1119-1131): out[b,i,c] = img[b, pix(b,i), c], 0 where rejected; out (B, N, C) contiguous,
+ * every element stored once. */
+#define PCOPS_COORD_F32 0
+#define PCOPS_COORD_F64 1
+#define PCOPS_COORD_I32 2
+#define PCOPS_COORD_I64 3
+int pcops_pixel_gather(const float *img, const void *coord, int coord_dtype, int B, int N, int C, int P,
+                       long long stride_b, long long stride_p, long long stride_c, float *out,
+                       pcops_stream_t stream);
+/* pcops_pixel_splat -- point_fea_img_fea (:1134-1154): out[b,p,c] = the fp32 sum, in
+ * ascending i, of fea[b,i,c] over the points with pix(b,i) == p; fea (B, N, C) contiguous.
+ * No float atomics: a stable counting sort of the points by pixel (workspace), then one
+ * in-order sum per output element, so the result is bitwise reproducible and equals a
+ * sequential scatter_add.  Every element of out is stored exactly once (0 for an empty
+ * pixel); the workspace may hold anything on entry.  The sort is one wave per cloud (N/64
+ * serial steps): made for many clouds of a few thousand points, slow for one cloud of tens of
+ * thousands.  workspace NULL or below pcops_pixel_splat_workspace_bytes:
+ * PCOPS_ERR_WORKSPACE, nothing is launched. */
+unsigned long long pcops_pixel_splat_workspace_bytes(int B, int N, int P);
+int pcops_pixel_splat(const float *fea, const void *coord, int coord_dtype, int B, int N, int C, int P, float *out,
+                      long long stride_b, long long stride_p, long long stride_c, void *workspace,
+                      unsigned long long workspace_bytes, pcops_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,11 @@ _SIGS = {
     "pcops_points2grid": (I, [P, P, P, P, I, I, I, I, I, P, P]),
     "pcops_grid2image_workspace_bytes": (ULL, [I, I, I]),
     "pcops_grid2image": (I, [P, P, I, I, I, P, P, ULL, P]),
+    "pcops_points2depth_backward": (I, [P, P, P, P, P, P, I, I, I, I, I, P, P]),
+    "pcops_points2pixel": (I, [P, P, P, I, I, I, I, I, P, P]),
+    "pcops_pixel_gather": (I, [P, P, I, I, I, I, I, LL, LL, LL, P, P]),
+    "pcops_pixel_splat_workspace_bytes": (ULL, [I, I, I]),
+    "pcops_pixel_splat": (I, [P, P, I, I, I, I, I, P, LL, LL, LL, P, ULL, P]),
 }
 
 

@@ -137,6 +137,13 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// Workgroups for a grid-stride loop over `total` elements: one element per thread up to 8192 workgroups.
+static inline unsigned grid_for(size_t total, int block) {
+  size_t g = (total + block - 1) / block;
+  if (g > 8192) g = 8192;
+  return (unsigned)(g < 1 ? 1 : g);
+}
+
 #define PC_CHECK_LAUNCH()                               \
   do {                                                  \
     hipError_t _e = hipGetLastError();                  \

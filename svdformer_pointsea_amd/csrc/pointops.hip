@@ -9,12 +9,6 @@
 
 namespace {
 
-unsigned grid_for(size_t total, int block) {
-  size_t g = (total + block - 1) / block;
-  if (g > 8192) g = 8192;
-  return (unsigned)(g < 1 ? 1 : g);
-}
-
 // out[b,c,s,k] = points[b,c,idx[b,s,k]]
 __global__ void group_kernel(const float *__restrict__ points, const int *__restrict__ idx, int C, int N, int SK,
                              size_t total, float *__restrict__ out) {

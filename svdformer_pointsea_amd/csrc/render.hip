@@ -6,7 +6,9 @@
 // atomics; a second pass forms the harmonic-mean depth.  The projection
 // arithmetic follows the reference's fp32 op order exactly (point @ R as an
 // fma chain = torch's sgemm order, then /, *, +, ceil), so every point lands
-// on the reference's pixel.
+// on the reference's pixel.  That arithmetic is one device function (depth_project), shared
+// with the gradient (pcops_points2depth_backward: a gather, one lane per point over the views,
+// through the depth only -- the pixel passes through ceil) and with pcops_points2pixel.
 //
 // PCViews_Real.get_img (models_PointSea/mv_utils_zs.py:97-195): one workgroup
 // per image transforms its cloud (two 3x3 products + translation), reduces the
@@ -25,6 +27,30 @@ __device__ __forceinline__ void xform(const float *R, float x, float y, float z,
   oz = __builtin_fmaf(z, R[8], __builtin_fmaf(y, R[5], x * R[2]));
 }
 
+// One (point, view) pair of the splat: transform, project, round to the pixel.  Returns false
+// where the splat rejects the pair (off canvas, or behind the camera); else `pix` is the pixel
+// ex*W + ey inside its image and `qz` the transformed depth.  The splat, its gradient and
+// pcops_points2pixel all call this, so they agree on the pixel bit for bit.
+__device__ __forceinline__ bool depth_project(const float *__restrict__ p, const float *__restrict__ R,
+                                              const float *__restrict__ t, int H, int W, float aspect, float &qz,
+                                              size_t &pix) {
+  const float eps = 1e-12f;
+  float qx, qy;
+  xform(R, p[0], p[1], p[2], qx, qy, qz);
+  qx = qx - t[0];
+  qy = qy - t[1];
+  qz = qz - t[2];
+  const float cx = (qx / (qz + eps)) * aspect;
+  const float cy = qy / (qz + eps);
+  const float xx = ((cx + 1.f) * (float)H) / 2.f;
+  const float yy = ((cy + 1.f) * (float)W) / 2.f;
+  const float ex = ceilf(xx + -0.5f);
+  const float ey = ceilf(yy + -0.5f);
+  if (!(ex >= 0.f && ex <= (float)(H - 1) && ey >= 0.f && ey <= (float)(W - 1) && qz >= 0.f)) return false;
+  pix = (size_t)ex * W + (size_t)ey;
+  return true;
+}
+
 __global__ void depth_splat_kernel(const float *__restrict__ points, const float *__restrict__ rot,
                                    const float *__restrict__ trans, int B, int N, int V, int H, int W,
                                    float *__restrict__ vsum, float *__restrict__ wsum) {
@@ -36,24 +62,67 @@ __global__ void depth_splat_kernel(const float *__restrict__ points, const float
     const size_t bv = e / N;
     const int v = (int)(bv % V);
     const size_t b = bv / V;
-    const float *p = points + (b * N + i) * 3;
-    const float *R = rot + v * 9;
-    float qx, qy, qz;
-    xform(R, p[0], p[1], p[2], qx, qy, qz);
-    qx = qx - trans[v * 3];
-    qy = qy - trans[v * 3 + 1];
-    qz = qz - trans[v * 3 + 2];
-    const float cx = (qx / (qz + eps)) * aspect;
-    const float cy = qy / (qz + eps);
-    const float xx = ((cx + 1.f) * (float)H) / 2.f;
-    const float yy = ((cy + 1.f) * (float)W) / 2.f;
-    const float ex = ceilf(xx + -0.5f);
-    const float ey = ceilf(yy + -0.5f);
-    if (!(ex >= 0.f && ex <= (float)(H - 1) && ey >= 0.f && ey <= (float)(W - 1) && qz >= 0.f)) continue;
+    float qz;
+    size_t px;
+    if (!depth_project(points + (b * N + i) * 3, rot + v * 9, trans + v * 3, H, W, aspect, qz, px)) continue;
     const float w = 1.f / (qz + eps);
-    const size_t pix = bv * (size_t)H * W + (size_t)ex * W + (size_t)ey;
+    const size_t pix = bv * (size_t)H * W + px;
     atomicAdd(wsum + pix, w);
     atomicAdd(vsum + pix, qz * w);
+  }
+}
+
+// Gradient of the resolved image with respect to the points: a gather, one lane per point.
+// Only the depth carries a gradient (the pixel goes through ceil): with w = 1/(z + eps),
+// Sw the pixel's weight sum after the "+1 where 0" rule and img = (sum z w) / Sw,
+//   d img / d z = w^2 (eps + img) / Sw,   z = p . rot[:, 2] - t_z,
+// so grad_p = sum over the views of g[pix] w^2 (eps + img[pix]) / Sw[pix] * rot_v[:, 2].
+// Every row is written once; a point rejected in every view gets exact zeros.
+__global__ void depth_backward_kernel(const float *__restrict__ points, const float *__restrict__ rot,
+                                      const float *__restrict__ trans, const float *__restrict__ img,
+                                      const float *__restrict__ wsum, const float *__restrict__ grad_img, int B, int N,
+                                      int V, int H, int W, float *__restrict__ grad_points) {
+  const size_t tot = (size_t)B * N;
+  const float eps = 1e-12f;
+  const float aspect = (float)((double)W / (double)H);
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < tot; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = e / N;
+    const float *p = points + e * 3;
+    float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+    for (int v = 0; v < V; ++v) {
+      const float *R = rot + v * 9;
+      float qz;
+      size_t px;
+      if (!depth_project(p, R, trans + v * 3, H, W, aspect, qz, px)) continue;
+      const size_t pix = (b * V + v) * (size_t)H * W + px;
+      const float w = 1.f / (qz + eps);
+      const float ws = wsum[pix];
+      const float dz = (((grad_img[pix] * w) * w) * (eps + img[pix])) / (ws == 0.f ? ws + 1.f : ws);
+      g0 = g0 + dz * R[2];
+      g1 = g1 + dz * R[5];
+      g2 = g2 + dz * R[8];
+    }
+    grad_points[e * 3] = g0;
+    grad_points[e * 3 + 1] = g1;
+    grad_points[e * 3 + 2] = g2;
+  }
+}
+
+// The splat's pixel of every (image, point) pair, -1 where the splat rejects it.
+__global__ void depth_pixel_kernel(const float *__restrict__ points, const float *__restrict__ rot,
+                                   const float *__restrict__ trans, int B, int N, int V, int H, int W,
+                                   long long *__restrict__ pixel) {
+  const size_t tot = (size_t)B * V * N;
+  const float aspect = (float)((double)W / (double)H);
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < tot; e += (size_t)gridDim.x * blockDim.x) {
+    const int i = (int)(e % N);
+    const size_t bv = e / N;
+    const int v = (int)(bv % V);
+    const size_t b = bv / V;
+    float qz;
+    size_t px;
+    const bool ok = depth_project(points + (b * N + i) * 3, rot + v * 9, trans + v * 3, H, W, aspect, qz, px);
+    pixel[e] = ok ? (long long)px : -1ll;
   }
 }
 
@@ -231,12 +300,6 @@ __global__ void image_normalize_kernel(const float *__restrict__ img, const int 
   }
 }
 
-unsigned grid_for(size_t total, int block) {
-  size_t g = (total + block - 1) / block;
-  if (g > 8192) g = 8192;
-  return (unsigned)(g < 1 ? 1 : g);
-}
-
 }  // namespace
 
 extern "C" unsigned long long pcops_points2depth_workspace_bytes(int B, int V, int H, int W) {
@@ -263,6 +326,31 @@ extern "C" int pcops_points2depth(const float *points, const float *rot, const f
     PC_CHECK_LAUNCH();
   }
   hipLaunchKernelGGL(depth_resolve_kernel, dim3(grid_for(tot, 256)), dim3(256), 0, s, img, wsum, tot);
+  PC_CHECK_LAUNCH();
+  return PCOPS_OK;
+}
+
+extern "C" int pcops_points2depth_backward(const float *points, const float *rot, const float *trans,
+                                           const float *img, const float *wsum, const float *grad_img, int B, int N,
+                                           int V, int H, int W, float *grad_points, pcops_stream_t stream) {
+  if (B < 0 || N < 0 || V < 0 || H <= 0 || W <= 0) return PCOPS_ERR_INVALID;
+  const size_t np = (size_t)B * N;
+  if (np == 0) return PCOPS_OK;
+  if (!points || !grad_points || (V > 0 && (!rot || !trans || !img || !wsum || !grad_img))) return PCOPS_ERR_INVALID;
+  hipLaunchKernelGGL(depth_backward_kernel, dim3(grid_for(np, 256)), dim3(256), 0, (hipStream_t)stream, points, rot,
+                     trans, img, wsum, grad_img, B, N, V, H, W, grad_points);
+  PC_CHECK_LAUNCH();
+  return PCOPS_OK;
+}
+
+extern "C" int pcops_points2pixel(const float *points, const float *rot, const float *trans, int B, int N, int V,
+                                  int H, int W, long long *pixel, pcops_stream_t stream) {
+  if (B < 0 || N < 0 || V < 0 || H <= 0 || W <= 0) return PCOPS_ERR_INVALID;
+  const size_t np = (size_t)B * V * N;
+  if (np == 0) return PCOPS_OK;
+  if (!points || !rot || !trans || !pixel) return PCOPS_ERR_INVALID;
+  hipLaunchKernelGGL(depth_pixel_kernel, dim3(grid_for(np, 256)), dim3(256), 0, (hipStream_t)stream, points, rot,
+                     trans, B, N, V, H, W, pixel);
   PC_CHECK_LAUNCH();
   return PCOPS_OK;
 }

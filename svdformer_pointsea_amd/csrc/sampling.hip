@@ -564,12 +564,6 @@ unsigned fps_excl_lds() {
   return bytes;
 }
 
-unsigned grid_for(size_t total, int block) {
-  size_t g = (total + block - 1) / block;
-  if (g > 8192) g = 8192;
-  return (unsigned)(g < 1 ? 1 : g);
-}
-
 unsigned grid_xcd(size_t total, int block) {  // a multiple of 8 workgroups (xcd_span)
   return (grid_for(total, block) + 7u) & ~7u;
 }

@@ -16,6 +16,7 @@ its model classes can import them unchanged:
   self_attention / cross_attention / SDG_Decoder        :542-629
   self_attention_woinp / SDG_Decoder_PointSea           models_PointSea/model_utils.py:463-509
   PCViews                                               :1179-1234
+  batched_index_select / point_fea_img_fea / distribute_img_fea_points   :1119-1176
 """
 import numpy as np
 import os
@@ -553,3 +554,158 @@ class PointNet_FP_Module(nn.Module):
 
     def forward_tokens(self, xyz1_t, xyz2_t, points1_t, points2_t):
         return self._run(xyz1_t, xyz2_t, None, points1_t, None, points2_t)
+
+
+# ---------------------------------------------------------------- point <-> pixel feature exchange
+_COORD_DTYPES = {torch.float32: 0, torch.float64: 1, torch.int32: 2, torch.int64: 3}
+
+
+def batched_index_select(inp, dim, index):
+    """models/model_utils.py:1119-1131: inp (B, *, ..., *), 0 < dim, index (B, M) -> inp gathered along
+    `dim` with the same M indices for every other axis."""
+    views = [inp.shape[0]] + [1 if i != dim else -1 for i in range(1, len(inp.shape))]
+    expanse = list(inp.shape)
+    expanse[0] = -1
+    expanse[dim] = -1
+    return torch.gather(inp, dim, index.view(views).expand(expanse))
+
+
+def _coord_mask(coord, P):
+    """The reference's mask (:1145-1146, :1167-1168) and the integer pixels with the rejected ones at 0."""
+    mask = (coord >= 0) * (coord <= P - 1)
+    return mask, torch.where(mask, coord, torch.zeros_like(coord)).long()
+
+
+def point_fea_img_fea_chain(point_fea, point_coo, h, w):
+    """The reference's expression (:1145-1152) without its in-place writes; torch ops, any device."""
+    mask, pix = _coord_mask(point_coo, h * w)
+    fea = torch.where(mask.unsqueeze(-1), point_fea, torch.zeros_like(point_fea))
+    bs, _, fs = fea.shape
+    return torch.zeros([bs, h * w, fs], device=fea.device, dtype=fea.dtype).scatter_add(
+        1, pix.unsqueeze(2).repeat([1, 1, fs]), fea)
+
+
+def distribute_img_fea_points_chain(img_fea, point_coord):
+    """The reference's expression (:1164-1175); torch ops, any device."""
+    B, C, H, W = list(img_fea.size())
+    rows = img_fea.permute(0, 2, 3, 1).reshape([B, H * W, C])
+    mask, pix = _coord_mask(point_coord, H * W)
+    fea = batched_index_select(inp=rows, dim=1, index=pix)
+    return torch.where(mask.unsqueeze(-1), fea, torch.zeros_like(fea))
+
+
+def _image_strides(t):
+    """(B,C,H,W) dense in NCHW or channels_last -> element strides (batch, pixel, channel), else None."""
+    B, C, H, W = t.shape
+    if t.is_contiguous():
+        return C * H * W, 1, H * W
+    if t.is_contiguous(memory_format=torch.channels_last):
+        return C * H * W, C, 1
+    return None
+
+
+def pixel_gather(img, strides, C, coord, P, out=None):
+    """pcops_pixel_gather: image side `img` of C channels addressed by element `strides` (batch, pixel,
+    channel), coord (B,N) -> (B,N,C)."""
+    B, N = coord.shape
+    out = torch.empty(B, N, C, device=coord.device) if out is None else out
+    with torch.cuda.device(coord.device):
+        call("pixel_gather", lib().pcops_pixel_gather, ptr(img), ptr(coord), _COORD_DTYPES[coord.dtype], B, N, C, P,
+             strides[0], strides[1], strides[2], ptr(out), stream_of(coord))
+    return out
+
+
+def pixel_splat(fea, coord, P, strides, out):
+    """pcops_pixel_splat: fea (B,N,C) contiguous, coord (B,N) -> `out`, whose image side is addressed by
+    element `strides` (batch, pixel, channel); the ordered (bitwise reproducible) scatter-sum."""
+    B, N, C = fea.shape
+    wsb = lib().pcops_pixel_splat_workspace_bytes(B, N, P)
+    ws = Workspace.get(fea.device, wsb)
+    with torch.cuda.device(fea.device):
+        call("pixel_splat", lib().pcops_pixel_splat, ptr(fea), ptr(coord), _COORD_DTYPES[coord.dtype], B, N, C, P,
+             ptr(out), strides[0], strides[1], strides[2], ptr(ws), wsb, stream_of(fea))
+    return out
+
+
+class _PixelSplat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, fea, coord, P):
+        B, N, C = fea.shape
+        ctx.save_for_backward(coord)
+        ctx.P = P
+        return pixel_splat(fea.contiguous(), coord, P, (P * C, C, 1), torch.empty(B, P, C, device=fea.device))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (coord,) = ctx.saved_tensors
+        g = g.contiguous()
+        C = g.shape[2]
+        return pixel_gather(g, (ctx.P * C, C, 1), C, coord, ctx.P), None, None
+
+
+class _PixelGather(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img, coord):
+        B, C, H, W = img.shape
+        ctx.save_for_backward(coord)
+        ctx.cl = not img.is_contiguous()
+        ctx.shape = img.shape
+        return pixel_gather(img, _image_strides(img), C, coord, H * W)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        (coord,) = ctx.saved_tensors
+        B, C, H, W = ctx.shape
+        # the gradient in the input's memory format, written in place by the splat's sum pass
+        gi = torch.empty(ctx.shape, device=g.device,
+                         memory_format=torch.channels_last if ctx.cl else torch.contiguous_format)
+        pixel_splat(g.contiguous(), coord, H * W, _image_strides(gi), gi)
+        return gi, None
+
+
+def _exchange_fused(fea, coord):
+    from .render import viewops_fused
+
+    return (viewops_fused() and fea.is_cuda and coord.is_cuda and fea.dtype == torch.float32
+            and coord.dtype in _COORD_DTYPES)
+
+
+def point_fea_img_fea(point_fea, point_coo, h, w):
+    """models/model_utils.py:1134-1154: splat per-point features into an h x w plane.
+    point_fea (B,N,C), point_coo (B,N), each coordinate x*w + y -> (B, h*w, C); differentiable in point_fea.
+
+    A coordinate c takes part iff 0 <= c <= h*w - 1 and lands on the pixel trunc(c); negative values,
+    >= h*w, NaN and +-inf contribute nothing.  On fp32 GPU tensors this is one ordered libpcops scatter-sum
+    (pcops_pixel_splat): each output element is the fp32 sum of its terms in ascending point index, bitwise
+    reproducible and equal to the reference's scatter_add run sequentially.  Other dtypes, CPU tensors and
+    PCOPS_VIEWOPS_FUSED=0 run the reference's torch chain.
+
+    Deliberate deviations from the reference: the inputs are NOT modified (the reference zeroes the rejected
+    entries of the caller's point_fea and point_coo in place); a rejected point adds nothing (the reference
+    adds 0 * fea to pixel 0, which differs only for a non-finite fea); integer coordinate dtypes are accepted
+    (the reference's in-place `*= mask.float()` raises on them)."""
+    assert len(point_fea.shape) == 3
+    assert len(point_coo.shape) == 2
+    assert point_fea.shape[0:2] == point_coo.shape
+    if not _exchange_fused(point_fea, point_coo):
+        return point_fea_img_fea_chain(point_fea, point_coo, h, w)
+    return _PixelSplat.apply(point_fea, point_coo.detach().contiguous(), h * w)
+
+
+def distribute_img_fea_points(img_fea, point_coord):
+    """models/model_utils.py:1157-1176: read image features back at the points.
+    img_fea (B,C,H,W), point_coord (B,N), each coordinate x*W + y -> (B,N,C), 0 for a point whose
+    coordinate is outside the image; differentiable in img_fea.
+
+    The index rule is point_fea_img_fea's.  On fp32 GPU tensors this is one libpcops row gather
+    (pcops_pixel_gather) that reads an NCHW or channels_last map in place, and its gradient is the ordered
+    scatter-sum written directly in the map's memory format.  Other dtypes, CPU tensors, maps dense in
+    neither format and PCOPS_VIEWOPS_FUSED=0 run the reference's torch chain.
+
+    Deliberate deviation from the reference: a rejected point reads 0 (the reference reads
+    0 * img[pixel 0], which differs only when that pixel is non-finite); the inputs are not modified."""
+    if not _exchange_fused(img_fea, point_coord) or _image_strides(img_fea) is None:
+        return distribute_img_fea_points_chain(img_fea, point_coord)
+    return _PixelGather.apply(img_fea, point_coord.detach().contiguous())

@@ -7,11 +7,21 @@ The view rotation matrices are built exactly as the reference builds them
 (euler2mat in torch float32, transposed); they are computed on the host CPU so
 the product path does not depend on the device's sin/cos.
 """
+import os
+
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import call, lib, ptr, require_float, stream_of
+
+# PCOPS_VIEWOPS_FUSED=0: the differentiable get_img and the point/pixel exchange ops of model_utils run the
+# reference's op chain in torch instead of the libpcops kernels (A/B runs, parity tests)
+_FUSED_ENV = "PCOPS_VIEWOPS_FUSED"
+
+
+def viewops_fused():
+    return os.environ.get(_FUSED_ENV, "1") != "0"
 
 
 def euler2mat(angle):
@@ -50,6 +60,14 @@ class PCViews:
         return self._dev[device]
 
     def get_img(self, points):
+        """Depth images of the three views.  When `points` needs a gradient the image is attached to the
+        graph (the reference's get_img is differentiable through the depth; the pixel coordinates pass
+        through ceil); otherwise this is the forward-only pass on the shared workspace."""
+        if points.requires_grad and torch.is_grad_enabled():
+            rot, trans = self._consts(points.device)
+            if not (viewops_fused() and points.is_cuda and points.dtype == torch.float32):
+                return points2depth_chain(points, rot, trans, self.resolution)
+            return _Points2Depth.apply(points, rot, trans, self.resolution)
         points = points.detach().contiguous()
         require_float(points, "points")
         B, N, _ = points.shape
@@ -62,6 +80,104 @@ class PCViews:
             call("points2depth", lib().pcops_points2depth, ptr(points), ptr(rot), ptr(trans), B, N, V, R, R, ptr(img),
                  ptr(ws), wsb, stream_of(points))
         return img
+
+    def project(self, points):
+        """(B,N,3) -> (B*3, N) int64: the pixel ex*R + ey get_img adds each point to in each view, -1 where
+        it rejects the point (off canvas, or behind the camera).  The coordinates point_fea_img_fea and
+        distribute_img_fea_points take, for these views."""
+        points = points.detach().contiguous()
+        if not (viewops_fused() and points.is_cuda and points.dtype == torch.float32):
+            return points2pixel_chain(points, *self._consts(points.device), self.resolution)
+        require_float(points, "points")
+        B, N, _ = points.shape
+        V, R = self.num_views, self.resolution
+        rot, trans = self._consts(points.device)
+        pix = torch.empty(B * V, N, dtype=torch.int64, device=points.device)
+        with torch.cuda.device(points.device):
+            call("points2pixel", lib().pcops_points2pixel, ptr(points), ptr(rot), ptr(trans), B, N, V, R, R, ptr(pix),
+                 stream_of(points))
+        return pix
+
+
+def _project_chain(points, rot, trans, R):
+    """point_transform (:1223-1234) and the projection of points2depth / distribute (:1093-1100, :1025-1041,
+    size 1) in the reference's op order -> depth, ex, ey, mask, each (B*V, N)."""
+    b, v = points.shape[0], rot.shape[0]
+    p = torch.matmul(torch.repeat_interleave(points, v, dim=0), rot.repeat(b, 1, 1))
+    p = p - trans.unsqueeze(1).repeat(b, 1, 1)
+    eps = torch.tensor([1e-12], device=points.device)
+    depth = p[:, :, 2]
+    coord_x = (p[:, :, 0] / (depth + eps)) * (R / R)
+    coord_y = p[:, :, 1] / (depth + eps)
+    _x = ((coord_x + 1) * R) / 2
+    _y = ((coord_y + 1) * R) / 2
+    ex = (_x + -0.5).ceil()
+    ey = (_y + -0.5).ceil()
+    mask = (ex >= 0) * (ex <= R - 1) * (ey >= 0) * (ey <= R - 1) * (depth >= 0)
+    return depth, ex, ey, mask
+
+
+def points2depth_chain(points, rot, trans, R):
+    """PCViews.get_img as the reference writes it (models/model_utils.py:1196-1234 -> points2depth
+    :1080-1115 -> distribute :1004-1077 with size_x = size_y = 1), in torch ops and in its op order:
+    points (B,N,3), rot (V,3,3) as stored (transposed), trans (V,3) -> (B*V, R, R).  Works on CPU and GPU
+    tensors and differentiates through autograd; the baseline the kernels are compared with."""
+    depth, ex, ey, mask = _project_chain(points, rot, trans, R)
+    bv = depth.shape[0]
+    eps = torch.tensor([1e-12], device=points.device)
+    # a rejected pair adds weight 0 at pixel 0 (the reference adds 0 at its wrapped pixel, and turns a
+    # non-finite pixel -- z + eps == 0 -- into an index); every kept pair is the reference's term at its pixel
+    weight = torch.where(mask, 1 / (depth + eps), torch.zeros_like(depth))
+    weighted = torch.where(mask, depth * weight, torch.zeros_like(depth))
+    coords = torch.where(mask, ex * R + ey, torch.zeros_like(ex)).long()
+    wsum = torch.zeros([bv, R * R], device=points.device).scatter_add(1, coords, weight)
+    wsum = wsum + (wsum == 0.0).float()
+    vsum = torch.zeros([bv, R * R], device=points.device).scatter_add(1, coords, weighted)
+    return (vsum / wsum).view([bv, R, R])
+
+
+def points2pixel_chain(points, rot, trans, R):
+    """The pixel ex*R + ey of every (image, point) pair, -1 where the mask rejects it: (B*V, N) int64."""
+    with torch.no_grad():
+        _, ex, ey, mask = _project_chain(points, rot, trans, R)
+        return torch.where(mask, (ex * R + ey), torch.full_like(ex, -1.0)).long()
+
+
+class _Points2Depth(torch.autograd.Function):
+    """pcops_points2depth with the weight-sum image kept (its `workspace` is a tensor of its own), and
+    pcops_points2depth_backward, a gather over (points, img, wsum)."""
+
+    @staticmethod
+    def forward(ctx, points, rot, trans, R):
+        pts = points.detach().contiguous()
+        B, N, _ = pts.shape
+        V = rot.shape[0]
+        img = torch.empty(B * V, R, R, device=pts.device)
+        wsum = torch.empty(B * V, R, R, device=pts.device)
+        with torch.cuda.device(pts.device):
+            call("points2depth", lib().pcops_points2depth, ptr(pts), ptr(rot), ptr(trans), B, N, V, R, R, ptr(img),
+                 ptr(wsum), wsum.numel() * 4, stream_of(pts))
+        ctx.save_for_backward(pts, rot, trans, img, wsum)
+        return img
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        pts, rot, trans, img, wsum = ctx.saved_tensors
+        return points2depth_backward(pts, rot, trans, img, wsum, g), None, None, None
+
+
+def points2depth_backward(points, rot, trans, img, wsum, grad_img, out=None):
+    """pcops_points2depth_backward: (B,N,3) gradient of the points from the saved image and weight sums."""
+    B, N, _ = points.shape
+    V, R = rot.shape[0], img.shape[-1]
+    g = grad_img.contiguous()
+    require_float(g, "grad_img")
+    gp = torch.empty_like(points) if out is None else out
+    with torch.cuda.device(points.device):
+        call("points2depth_backward", lib().pcops_points2depth_backward, ptr(points), ptr(rot), ptr(trans), ptr(img),
+             ptr(wsum), ptr(g), B, N, V, R, R, ptr(gp), stream_of(points))
+    return gp
 
 
 # mv_utils_zs.py:9-14
@@ -90,7 +206,11 @@ def get3DGaussianKernel(ksize, depth, sigma=2, zsigma=2):
 
 
 class PCViews_Real:
-    """get_img(points (B,N,3)) -> (B*3, 3, 224, 224) PointSea 'realistic' depth images."""
+    """get_img(points (B,N,3)) -> (B*3, 3, 224, 224) PointSea 'realistic' depth images.
+
+    Forward-only: the points are detached.  A gradient would have to run through a scatter-max of clipped
+    depths and the bounding-box normalisation, and nothing trains through this renderer (unlike
+    PCViews.get_img, which is differentiable)."""
 
     def __init__(self, TRANS=-0.7):
         _views = np.asarray([

@@ -200,6 +200,47 @@ unsigned long long pcops_knn_workspace_bytes(int B, int S, int N, int C, int K);
 int pcops_knn_ws(const float *q, const float *p, int B, int S, int N, int C, int K, int pad, int *idx, float *dist,
                  void *workspace, unsigned long long workspace_bytes, pcops_stream_t stream);
 
+/* ---------------- Neighbour distances (models/model_utils.py:288-321, :501-521) ----------------
+ * nearest_distances (:288-297), self_nearest_distances (:299-307), self_nearest_distances_K
+ * (:309-321) and get_nearest_index (:501-521) without their (B,S,N) matrix: pcops_knn's scan on
+ * the operands as those callers hold them, CHANNEL-MAJOR q (B,3,S), p (B,3,N) fp32.
+ * pcops_nn_dist_forward selects, for every query, the K smallest d_ij in ascending (distance,
+ * index) order (an exact tie goes to the lower index).  With dot the sequential fma chain over
+ * x, y, z and |v|^2 = (x^2 + y^2) + z^2, the bits of torch's CPU kernels:
+ *   form 0 (A)  d = ((-2 dot) + |q|^2) + |p|^2     nearest_distances, self_*, square_distance
+ *   form 1 (B)  d = (|p|^2 + |q|^2) - 2 dot        get_nearest_index
+ *   self_diag   2.0f is ADDED to the candidate whose index is the query's (`eye * 2`, :304, :314:
+ *               an addition, not an exclusion -- the diagonal can still be the minimum); needs
+ *               S == N, the caller passes the same cloud twice
+ *   reduce 0    val (B,S,K) = the K distances
+ *   reduce 1    val (B,S)   = sqrt((...(d_0 + d_1) + ... + d_{K-1}) / (float)K), rank order, the
+ *               division and the square root correctly rounded (K == 1: sqrt(d_0); NaN exactly
+ *               where that minimum is negative, as the reference's sqrt)
+ * idx (B,S,K) int32 is always written (the backward reads it).  K <= 64 (above:
+ * PCOPS_ERR_UNSUPPORTED); K > N, self_diag with S != N, B > 65535: PCOPS_ERR_INVALID; empty B, S
+ * or K: PCOPS_OK, nothing launched.  No workspace.
+ *
+ * pcops_nn_dist_backward: with c_ik the gradient arriving on d_ik -- reduce 0: c = grad (B,S,K);
+ * reduce 1: c = (grad[i] / (2 val[i])) / K from the forward's val (B,S) and grad (B,S) -- and
+ * t_ik = c_ik * (2 (q_i - p_j)), j = idx_ik, taken as 0 for a diagonal pair (self_diag, j == i):
+ *   grad_q[:, i] = ((0 + t_i0) + t_i1) + ...            (B,3,S), rank order, no cross-thread sum
+ *   grad_p[:, j] = sum of -t_ik over idx_ik == j        (B,3,N), added in ascending (i, k)
+ * The target-side sum is an ORDERED sum (pcops_pixel_splat's stable counting sort over the pair
+ * list in the workspace), not an atomic one: the same bits on every run.  same != 0: q and p are
+ * one tensor (S == N); both sums land in grad_p (grad_q is not written), the query side of row i
+ * entering target i's ordered sum after the row's K pairs.  grad_q or grad_p may be NULL (that
+ * side is not computed); what is given is fully overwritten.  A row whose val is 0 or NaN carries
+ * non-finite terms, as in the reference: they reach that row of grad_q and the targets the row
+ * points at, nothing else.  workspace: pcops_nn_dist_backward_workspace_bytes (only read when
+ * grad_p is given); too small: PCOPS_ERR_WORKSPACE. */
+int pcops_nn_dist_forward(const float *q, const float *p, int B, int S, int N, int K, int form, int self_diag,
+                          int reduce, int *idx, float *val, pcops_stream_t stream);
+unsigned long long pcops_nn_dist_backward_workspace_bytes(int B, int S, int N, int K, int same);
+int pcops_nn_dist_backward(const float *q, const float *p, const int *idx, const float *val, const float *grad,
+                           int B, int S, int N, int K, int self_diag, int reduce, int same, float *grad_q,
+                           float *grad_p, void *workspace, unsigned long long workspace_bytes,
+                           pcops_stream_t stream);
+
 /* ---------------- Chamfer (metrics/CD/chamfer3D) ----------------
  * chamfer_3D.forward(xyz1, xyz2, dist1, dist2, idx1, idx2): chamfer_cuda.cpp:17-33,
  * chamfer3D.cu:12-154. */

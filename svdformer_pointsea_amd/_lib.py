@@ -46,6 +46,9 @@ _SIGS = {
     "pcops_knn": (I, [P, P, I, I, I, I, I, I, P, P, P]),
     "pcops_knn_workspace_bytes": (ULL, [I, I, I, I, I]),
     "pcops_knn_ws": (I, [P, P, I, I, I, I, I, I, P, P, P, ULL, P]),
+    "pcops_nn_dist_forward": (I, [P, P, I, I, I, I, I, I, I, P, P, P]),
+    "pcops_nn_dist_backward_workspace_bytes": (ULL, [I, I, I, I, I]),
+    "pcops_nn_dist_backward": (I, [P, P, P, P, P, I, I, I, I, I, I, I, P, P, P, ULL, P]),
     "pcops_chamfer_forward": (I, [P, P, I, I, I, P, P, P, P, P]),
     "pcops_chamfer_workspace_bytes": (ULL, [I, I, I]),
     "pcops_chamfer_forward_ws": (I, [P, P, I, I, I, P, P, P, P, P, ULL, P]),

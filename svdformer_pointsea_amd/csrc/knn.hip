@@ -208,10 +208,27 @@ __device__ __forceinline__ float next_up(float x) {
 // Large grids (>= 3 blocks per CU): G = 4, TN = 512 -> 40 KB of LDS, so four
 // blocks (16 waves) fit a CU and the whole grid is resident at once; small
 // grids: G = 8 waves per 64 queries, TN = 1024.
-template <int KK, int G, int TN>
+//
+// The scan has two compile-time variants (`if constexpr` on V: neither instantiation carries a
+// branch of the other).  ScanKnn is pcops_knn's: token-major operands, form A, `flags` unused.
+// ScanNN is pcops_nn_dist_forward's (models/model_utils.py:288-321, :501-521): channel-major
+// operands (B,3,S) / (B,3,N) as those callers hold them, and in `flags`
+//   NN_FORM_B  d = (|p|^2 + |q|^2) + (-2 dot)   instead of form A's ((-2 dot) + |q|^2) + |p|^2
+//   NN_DIAG    + 2.0f on the candidate whose index is the query's (the reference's `eye * 2`)
+//   NN_ROOT    the K sorted distances stay in LDS; `dist` (B,S) gets sqrt((d_0 + ... + d_{K-1}) / K),
+//              summed in rank order, division and square root correctly rounded
+struct ScanKnn {
+  static constexpr bool nn = false;
+};
+struct ScanNN {
+  static constexpr bool nn = true;
+};
+enum { NN_FORM_B = 1, NN_DIAG = 2, NN_ROOT = 4 };
+
+template <int KK, int G, int TN, class V = ScanKnn>
 __global__ __launch_bounds__(64 * G) void knn3_kernel(const float *__restrict__ q, const float *__restrict__ p, int S,
                                                       int N, int K, int pad, int *__restrict__ idx,
-                                                      float *__restrict__ dist, bool share) {
+                                                      float *__restrict__ dist, bool share, int flags) {
   // CAP 15 leaves room for the shared thresholds inside the merge buffer's footprint
   // (40 KB at G = 4, TN = 512: four blocks per CU)
   constexpr int SL = TN / G, U = 8, CAP = 15, NT = 64 * G;
@@ -229,7 +246,13 @@ __global__ __launch_bounds__(64 * G) void knn3_kernel(const float *__restrict__ 
   const float *qb = q + (size_t)b * S * 3;
   const float *pb = p + (size_t)b * N * 3;
   const int sc = s < S ? s : S - 1;
-  const float qx = qb[3 * sc], qy = qb[3 * sc + 1], qz = qb[3 * sc + 2];
+  float qx, qy, qz;
+  if constexpr (V::nn) {
+    static_assert(TN * sizeof(float4) >= 64 * KK * sizeof(float), "the tile holds the root's sorted rows");
+    qx = qb[sc], qy = qb[(size_t)S + sc], qz = qb[2 * (size_t)S + sc];
+  } else {
+    qx = qb[3 * sc], qy = qb[3 * sc + 1], qz = qb[3 * sc + 2];
+  }
   const float qn = (qx * qx + qy * qy) + qz * qz;
   const float mx = -2.f * qx, my = -2.f * qy, mz = -2.f * qz;  // (-2q).p == -2(q.p) bit-exactly
   TopK<KK, CAP, NT> tk;
@@ -247,8 +270,14 @@ __global__ __launch_bounds__(64 * G) void knn3_kernel(const float *__restrict__ 
   for (int t0 = 0; t0 < N; t0 += TN) {
     const int cnt = min(TN, N - t0);
     for (int e = tid; e < cnt; e += NT) {
-      const float *src = pb + (size_t)(t0 + e) * 3;
-      const float x = src[0], y = src[1], z = src[2];
+      float x, y, z;
+      if constexpr (V::nn) {
+        const float *src = pb + t0 + e;
+        x = src[0], y = src[(size_t)N], z = src[2 * (size_t)N];
+      } else {
+        const float *src = pb + (size_t)(t0 + e) * 3;
+        x = src[0], y = src[1], z = src[2];
+      }
       tile[e] = make_float4(x, y, z, (x * x + y * y) + z * z);
     }
     __syncthreads();
@@ -270,6 +299,10 @@ __global__ __launch_bounds__(64 * G) void knn3_kernel(const float *__restrict__ 
         if (live && dd < tk.bd[0]) { tk.bd[0] = dd; tk.bi[0] = t0 + e0 + u; }
 #else
         float d = (dot + qn) + c[u].w;
+        if constexpr (V::nn) {
+          if (flags & NN_FORM_B) d = (c[u].w + qn) + dot;           // wave-uniform
+          if (flags & NN_DIAG) d = t0 + e0 + u == s ? d + 2.f : d;  // s: this lane's query
+        }
         asm volatile("" : "+v"(d));  // keep the chains scalar (SLP paired them into v_pk_* + moves)
         tk.append(sh.sc.queue, tid, d, t0 + e0 + u, live && d < teff);
 #endif
@@ -298,6 +331,19 @@ __global__ __launch_bounds__(64 * G) void knn3_kernel(const float *__restrict__ 
     __syncthreads();
   }
   tk.drain(sh.sc.queue, tid);
+  if constexpr (V::nn) {
+    if (flags & NN_ROOT) {
+      // the scan's last barrier freed the tile: wave 0 keeps each query's sorted row there
+      float *row = reinterpret_cast<float *>(tile) + lane * K;
+      merge_and_store<KK, G>(sh.mb, tk.bd, tk.bi, w, lane, s < S, K, 0, N, idx + ((size_t)b * S + sc) * K, row);
+      if (w == 0 && s < S) {
+        float acc = row[0];
+        for (int k = 1; k < K; ++k) acc = acc + row[k];
+        dist[(size_t)b * S + s] = __builtin_sqrtf(acc / (float)K);
+      }
+      return;
+    }
+  }
   merge_and_store<KK, G>(sh.mb, tk.bd, tk.bi, w, lane, s < S, K, pad, N, idx + ((size_t)b * S + sc) * K,
                          dist ? dist + ((size_t)b * S + sc) * K : nullptr);
 }
@@ -685,24 +731,24 @@ bool knn_share_on() {  // PCOPS_KNN_SHARE=0: no cross-wave threshold sharing (A/
   return v;
 }
 
-template <int KK>
+template <int KK, class V = ScanKnn>
 int launch_knn(const float *q, const float *p, int B, int S, int N, int C, int K, int pad, int *idx, float *dist,
-               hipStream_t st) {
+               hipStream_t st, int flags = 0) {
   constexpr int G = KK <= 16 ? 4 : (KK <= 32 ? 2 : 1);
   const dim3 grid((S + 63) / 64, B);
   if (C == 3) {
     if constexpr (KK <= 16) {
       if ((long)grid.x * grid.y < 768) {  // < 3 blocks per CU: more waves per query
-        hipLaunchKernelGGL((knn3_kernel<KK, 8, 1024>), grid, dim3(512), 0, st, q, p, S, N, K, pad, idx, dist,
-                           knn_share_on());
+        hipLaunchKernelGGL((knn3_kernel<KK, 8, 1024, V>), grid, dim3(512), 0, st, q, p, S, N, K, pad, idx, dist,
+                           knn_share_on(), flags);
         PC_CHECK_LAUNCH();
         return PCOPS_OK;
       }
-      hipLaunchKernelGGL((knn3_kernel<KK, 4, 512>), grid, dim3(256), 0, st, q, p, S, N, K, pad, idx, dist,
-                         knn_share_on());
+      hipLaunchKernelGGL((knn3_kernel<KK, 4, 512, V>), grid, dim3(256), 0, st, q, p, S, N, K, pad, idx, dist,
+                         knn_share_on(), flags);
     } else {
-      hipLaunchKernelGGL((knn3_kernel<KK, G, 1024>), grid, dim3(64 * G), 0, st, q, p, S, N, K, pad, idx, dist,
-                         knn_share_on());
+      hipLaunchKernelGGL((knn3_kernel<KK, G, 1024, V>), grid, dim3(64 * G), 0, st, q, p, S, N, K, pad, idx, dist,
+                         knn_share_on(), flags);
     }
     PC_CHECK_LAUNCH();
     return PCOPS_OK;
@@ -825,4 +871,137 @@ extern "C" int pcops_knn(const float *q, const float *p, int B, int S, int N, in
   if (kk <= 32) return launch_knn<32>(q, p, B, S, N, C, K, pad, idx, dist, st);
   if (kk <= 64) return launch_knn<64>(q, p, B, S, N, C, K, pad, idx, dist, st);
   return PCOPS_ERR_UNSUPPORTED;
+}
+
+// ------------------------------------------------- neighbour distances (model_utils.py:288-321, :501-521)
+namespace {
+
+// One thread per query: the K pairs' gradient terms t_k = c_k * (2 (q_i - p_j)), j = idx[i][k], with
+//   reduce none: c_k = g[i][k];   root: c = (g[i] / (2 val[i])) / K for every k (SqrtBackward, MeanBackward)
+// and t_k = 0 for a diagonal pair (self_diag, j == i).  grad_q[:, i] = ((0 + t_0) + t_1) + ... in rank
+// order.  The target side is not summed here: the pair's row -t_k and its target j (-1 for a diagonal pair:
+// the splat rejects it) go to `rows` / `tgt`, K1 slots per query, and pcops_pixel_splat adds each target's
+// rows in ascending slot order.  same (q and p one tensor): slot K of a query holds its own sum with
+// target i, so both sides land in one output, still in one fixed order.
+__global__ __launch_bounds__(256) void nn_dist_pairs_kernel(const float *__restrict__ q, const float *__restrict__ p,
+                                                            const int *__restrict__ idx,
+                                                            const float *__restrict__ val,
+                                                            const float *__restrict__ g, int B, int S, int N, int K,
+                                                            bool self_diag, bool root, bool same,
+                                                            float *__restrict__ grad_q, float *__restrict__ rows,
+                                                            int *__restrict__ tgt) {
+  const size_t tot = (size_t)B * S;
+  const int K1 = K + (same ? 1 : 0);
+  for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < tot; r += (size_t)gridDim.x * blockDim.x) {
+    const size_t b = r / S;
+    const int i = (int)(r - b * S);
+    const float *qb = q + b * 3 * (size_t)S;
+    const float *pb = p + b * 3 * (size_t)N;
+    const float qx = qb[i], qy = qb[(size_t)S + i], qz = qb[2 * (size_t)S + i];
+    float c = 0.f;
+    if (root) c = (g[r] / (2.f * val[r])) / (float)K;
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    for (int k = 0; k < K; ++k) {
+      const int j = idx[r * K + k];
+      if (!root) c = g[r * K + k];
+      const bool diag = self_diag && j == i;
+      const bool in = j >= 0 && j < N;  // an index outside the cloud is never an address
+      const int jc = in ? j : 0;
+      float tx = c * (2.f * (qx - pb[jc]));
+      float ty = c * (2.f * (qy - pb[(size_t)N + jc]));
+      float tz = c * (2.f * (qz - pb[2 * (size_t)N + jc]));
+      if (diag || !in) tx = ty = tz = 0.f;
+      ax = ax + tx;
+      ay = ay + ty;
+      az = az + tz;
+      if (rows) {
+        float *row = rows + (r * K1 + k) * 3;
+        row[0] = -tx;
+        row[1] = -ty;
+        row[2] = -tz;
+        tgt[r * K1 + k] = (diag || !in) ? -1 : j;
+      }
+    }
+    if (same) {
+      float *row = rows + (r * K1 + K) * 3;
+      row[0] = ax;
+      row[1] = ay;
+      row[2] = az;
+      tgt[r * K1 + K] = i;
+    } else if (grad_q) {
+      float *gq = grad_q + b * 3 * (size_t)S;
+      gq[i] = ax;
+      gq[(size_t)S + i] = ay;
+      gq[2 * (size_t)S + i] = az;
+    }
+  }
+}
+
+size_t nn_align(size_t x) { return (x + 255) & ~size_t(255); }
+
+}  // namespace
+
+extern "C" int pcops_nn_dist_forward(const float *q, const float *p, int B, int S, int N, int K, int form,
+                                     int self_diag, int reduce, int *idx, float *val, pcops_stream_t stream) {
+  if (B < 0 || S < 0 || N < 0 || K < 0 || form < 0 || form > 1 || reduce < 0 || reduce > 1)
+    return PCOPS_ERR_INVALID;
+  if (K > 64) return PCOPS_ERR_UNSUPPORTED;
+  if (B == 0 || S == 0 || K == 0) return PCOPS_OK;
+  if (!q || !p || !idx || !val || K > N || (self_diag && S != N) || B > 65535) return PCOPS_ERR_INVALID;
+  const int flags = (form ? NN_FORM_B : 0) | (self_diag ? NN_DIAG : 0) | (reduce ? NN_ROOT : 0);
+  hipStream_t st = (hipStream_t)stream;
+  if (K <= 4) return launch_knn<4, ScanNN>(q, p, B, S, N, 3, K, 0, idx, val, st, flags);
+  if (K <= 8) return launch_knn<8, ScanNN>(q, p, B, S, N, 3, K, 0, idx, val, st, flags);
+  if (K <= 16) return launch_knn<16, ScanNN>(q, p, B, S, N, 3, K, 0, idx, val, st, flags);
+  if (K <= 20) return launch_knn<20, ScanNN>(q, p, B, S, N, 3, K, 0, idx, val, st, flags);
+  if (K <= 32) return launch_knn<32, ScanNN>(q, p, B, S, N, 3, K, 0, idx, val, st, flags);
+  return launch_knn<64, ScanNN>(q, p, B, S, N, 3, K, 0, idx, val, st, flags);
+}
+
+extern "C" unsigned long long pcops_nn_dist_backward_workspace_bytes(int B, int S, int N, int K, int same) {
+  if (B <= 0 || S <= 0 || N <= 0 || K <= 0) return 0;
+  const long long slots = (long long)S * (K + (same ? 1 : 0));
+  if (slots > INT_MAX) return 0;
+  const size_t pairs = (size_t)B * slots;
+  return nn_align(pairs * 3 * sizeof(float)) + nn_align(pairs * sizeof(int)) +
+         pcops_pixel_splat_workspace_bytes(B, (int)slots, N);
+}
+
+extern "C" int pcops_nn_dist_backward(const float *q, const float *p, const int *idx, const float *val,
+                                      const float *grad, int B, int S, int N, int K, int self_diag, int reduce,
+                                      int same, float *grad_q, float *grad_p, void *workspace,
+                                      unsigned long long workspace_bytes, pcops_stream_t stream) {
+  if (B < 0 || S < 0 || N < 0 || K < 0 || reduce < 0 || reduce > 1) return PCOPS_ERR_INVALID;
+  if (same && S != N) return PCOPS_ERR_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  if (B == 0) return PCOPS_OK;
+  if (S == 0 || K == 0) {  // no pairs: the outputs are still fully written
+    if (grad_q && pc_memset_async(grad_q, 0, (size_t)B * 3 * S * sizeof(float), st)) return PCOPS_ERR_LAUNCH;
+    if (grad_p && pc_memset_async(grad_p, 0, (size_t)B * 3 * N * sizeof(float), st)) return PCOPS_ERR_LAUNCH;
+    return PCOPS_OK;
+  }
+  if (!q || !p || !idx || !grad || (reduce && !val) || N <= 0 || (same && !grad_p)) return PCOPS_ERR_INVALID;
+  if (!grad_q && !grad_p) return PCOPS_OK;
+  const int K1 = K + (same ? 1 : 0);
+  if ((long long)S * K1 > INT_MAX) return PCOPS_ERR_UNSUPPORTED;
+  float *rows = nullptr;
+  int *tgt = nullptr;
+  char *splat_ws = nullptr;
+  unsigned long long splat_bytes = 0;
+  if (grad_p) {
+    const unsigned long long need = pcops_nn_dist_backward_workspace_bytes(B, S, N, K, same);
+    if (!workspace || workspace_bytes < need) return PCOPS_ERR_WORKSPACE;
+    const size_t pairs = (size_t)B * S * K1;
+    rows = (float *)workspace;
+    tgt = (int *)((char *)workspace + nn_align(pairs * 3 * sizeof(float)));
+    splat_ws = (char *)tgt + nn_align(pairs * sizeof(int));
+    splat_bytes = need - (unsigned long long)(splat_ws - (char *)workspace);
+  }
+  hipLaunchKernelGGL(nn_dist_pairs_kernel, dim3(grid_for((size_t)B * S, 256)), dim3(256), 0, st, q, p, idx, val, grad,
+                     B, S, N, K, self_diag != 0, reduce != 0, same != 0, grad_q, rows, tgt);
+  PC_CHECK_LAUNCH();
+  if (!grad_p) return PCOPS_OK;
+  // grad_p (B,3,N): batch stride 3N, target stride 1, channel stride N
+  return pcops_pixel_splat(rows, tgt, PCOPS_COORD_I32, B, S * K1, 3, N, grad_p, 3ll * N, 1, N, splat_ws, splat_bytes,
+                           stream);
 }

@@ -17,6 +17,14 @@ its model classes can import them unchanged:
   self_attention_woinp / SDG_Decoder_PointSea           models_PointSea/model_utils.py:463-509
   PCViews                                               :1179-1234
   batched_index_select / point_fea_img_fea / distribute_img_fea_points   :1119-1176
+  nearest_distances(x, y)                               :288-297
+  self_nearest_distances(x)                             :299-307
+  self_nearest_distances_K(x, k=3)                      :309-321
+  get_nearest_index(target, source, k=1, return_dis=False)   :501-521
+  indexing_neighbor(x, index)                           :523-540
+  nn_dist_raw (the fused scan's distances and indices, no autograd)   :288-321, 501-521
+  square_distance / knn / get_graph_feature             :258-279, 911-943
+  MLP / MLP_Res / PointNetFeatureExtractor              :45-60, 79-95, 631-805
 """
 import numpy as np
 import os
@@ -709,3 +717,328 @@ def distribute_img_fea_points(img_fea, point_coord):
     if not _exchange_fused(img_fea, point_coord) or _image_strides(img_fea) is None:
         return distribute_img_fea_points_chain(img_fea, point_coord)
     return _PixelGather.apply(img_fea, point_coord.detach().contiguous())
+
+
+# ---------------------------------------------------------------- neighbour distances
+# PCOPS_NEIGHBOURS_FUSED=0: the reference's torch expressions (the *_chain functions) everywhere --
+# A/B runs and the parity tests.  With the switch on, a call still takes the chain when its operands
+# are not fp32 CUDA tensors, when C != 3, when K > NN_DIST_MAX_K or when B > NN_DIST_MAX_B.
+_NEIGHBOURS_FUSED = os.environ.get("PCOPS_NEIGHBOURS_FUSED", "1") != "0"
+NN_DIST_MAX_K = 64   # pcops_knn's list limit
+NN_DIST_MAX_B = 65535   # the batch is the scan's grid.y
+
+
+def _nn_check(q, p, k):
+    if q.dim() != 3 or p.dim() != 3 or q.shape[0] != p.shape[0] or q.shape[1] != p.shape[1]:
+        raise RuntimeError(f"neighbour distances: shape mismatch {tuple(q.shape)} vs {tuple(p.shape)}")
+    if k > p.shape[2]:
+        raise RuntimeError(f"selected index k out of range (k={k}, N={p.shape[2]})")
+
+
+def _nn_fused(q, p, k):
+    return (_NEIGHBOURS_FUSED and q.is_cuda and p.is_cuda and q.dtype == torch.float32 and p.dtype == torch.float32
+            and q.shape[1] == 3 and 1 <= k <= NN_DIST_MAX_K and q.shape[0] <= NN_DIST_MAX_B)
+
+
+def _nn_forward(q, p, k, form, self_diag, root):
+    """pcops_nn_dist_forward on contiguous fp32 q (B,3,S), p (B,3,N) -> val (B,S) | (B,S,k), idx int32."""
+    B, _, S = q.shape
+    N = p.shape[2]
+    if self_diag and S != N:
+        raise RuntimeError(f"self_diag needs one cloud, got {S} and {N} points")
+    val = torch.empty((B, S) if root else (B, S, k), dtype=torch.float32, device=q.device)
+    idx = torch.empty(B, S, k, dtype=torch.int32, device=q.device)
+    with torch.cuda.device(q.device):
+        call("nn_dist_forward", lib().pcops_nn_dist_forward, ptr(q), ptr(p), B, S, N, k, 1 if form == "B" else 0,
+             int(bool(self_diag)), int(bool(root)), ptr(idx), ptr(val), stream_of(q))
+    return val, idx
+
+
+def nn_dist_raw(q, p, k, form="A", self_diag=False):
+    """The k smallest squared distances of every query, no autograd: q (B,3,S), p (B,3,N) fp32 on the GPU
+    -> (distances (B,S,k) fp32, idx (B,S,k) int32) in ascending (distance, index) order.
+    form "A": ((-2 dot) + |q|^2) + |p|^2 (nearest_distances, square_distance); "B": (|p|^2 + |q|^2) - 2 dot
+    (get_nearest_index); self_diag adds 2 to the candidate whose index is the query's (S == N)."""
+    if form not in ("A", "B"):
+        raise ValueError(f"form must be 'A' or 'B', got {form!r}")
+    _nn_check(q, p, k)
+    q, p = q.detach().contiguous(), p.detach().contiguous()
+    require_float(q, "q")
+    require_float(p, "p")
+    if q.shape[1] != 3 or k > NN_DIST_MAX_K:
+        raise RuntimeError(f"nn_dist_raw: C == 3 and k <= {NN_DIST_MAX_K} only (C={q.shape[1]}, k={k})")
+    return _nn_forward(q, p, k, form, self_diag, False)
+
+
+class _NNDist(torch.autograd.Function):
+    """pcops_nn_dist_forward / _backward.  p None: the cloud against itself (one gradient)."""
+
+    @staticmethod
+    def forward(ctx, q, p, k, form, self_diag, root):
+        same = p is None
+        q = q.contiguous()
+        pc = q if same else p.contiguous()
+        val, idx = _nn_forward(q, pc, k, form, self_diag, root)
+        ctx.save_for_backward(q, pc, idx, val if root else None)
+        ctx.cfg = (k, bool(self_diag), bool(root), same)
+        ctx.mark_non_differentiable(idx)
+        return val, idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _gidx):
+        q, p, idx, val = ctx.saved_tensors
+        k, self_diag, root, same = ctx.cfg
+        B, _, S = q.shape
+        N = p.shape[2]
+        want_q = ctx.needs_input_grad[0] and not same
+        want_p = ctx.needs_input_grad[0] if same else ctx.needs_input_grad[1]
+        if not (want_q or want_p):
+            return None, None, None, None, None, None
+        g = g.float().contiguous()
+        gq = torch.empty_like(q) if want_q else None
+        gp = torch.empty_like(p) if want_p else None
+        with torch.cuda.device(q.device):
+            wsb = lib().pcops_nn_dist_backward_workspace_bytes(B, S, N, k, int(same)) if want_p else 0
+            ws = Workspace.get(q.device, wsb) if wsb else None
+            call("nn_dist_backward", lib().pcops_nn_dist_backward, ptr(q), ptr(p), ptr(idx), ptr(val), ptr(g), B, S, N,
+                 k, int(self_diag), int(root), int(same), ptr(gq), ptr(gp), ptr(ws), wsb, stream_of(q))
+        return (gp if same else gq), (None if same else gp), None, None, None, None
+
+
+def square_distance(src, dst):
+    """models/model_utils.py:258-279: src (B,N,C), dst (B,M,C) -> the (B,N,M) squared distances
+    ((-2 src.dst) + |src|^2) + |dst|^2; the torch expression (a full matrix is what it returns)."""
+    B, N, _ = src.shape
+    _, M, _ = dst.shape
+    dist = -2 * torch.matmul(src, dst.permute(0, 2, 1))
+    dist += torch.sum(src ** 2, -1).view(B, N, 1)
+    dist += torch.sum(dst ** 2, -1).view(B, 1, M)
+    return dist
+
+
+def nearest_distances_chain(x, y):
+    """models/model_utils.py:288-297, line for line."""
+    inner = -2 * torch.matmul(x.transpose(2, 1), y)
+    xx = torch.sum(x ** 2, dim=1, keepdim=True)
+    yy = torch.sum(y ** 2, dim=1, keepdim=True)
+    pairwise_distance = xx.transpose(2, 1) + inner + yy
+    return torch.sqrt(torch.min(pairwise_distance, dim=2, keepdim=True).values)
+
+
+def self_nearest_distances_chain(x):
+    """models/model_utils.py:299-307, line for line."""
+    inner = -2 * torch.matmul(x.transpose(2, 1), x)
+    xx = torch.sum(x ** 2, dim=1, keepdim=True)
+    pairwise_distance = xx.transpose(2, 1) + inner + xx
+    pairwise_distance += torch.eye(x.shape[2]).to(pairwise_distance.device) * 2
+    return torch.sqrt(torch.min(pairwise_distance, dim=2, keepdim=True).values)
+
+
+def self_nearest_distances_K_chain(x, k=3):
+    """models/model_utils.py:309-321, line for line."""
+    inner = -2 * torch.matmul(x.transpose(2, 1), x)
+    xx = torch.sum(x ** 2, dim=1, keepdim=True)
+    pairwise_distance = xx.transpose(2, 1) + inner + xx
+    pairwise_distance += torch.eye(x.shape[2]).to(pairwise_distance.device) * 2
+    pairwise_distance *= -1
+    k_nearest_distance = pairwise_distance.topk(k=k, dim=2)[0]
+    k_nearest_distance *= -1
+    return torch.sqrt(torch.mean(k_nearest_distance, dim=2, keepdim=True))
+
+
+def get_nearest_index_chain(target, source, k=1, return_dis=False):
+    """models/model_utils.py:501-521, line for line."""
+    inner = torch.bmm(target.transpose(1, 2), source)
+    s_norm_2 = torch.sum(source ** 2, dim=1)
+    t_norm_2 = torch.sum(target ** 2, dim=1)
+    d_norm_2 = s_norm_2.unsqueeze(1) + t_norm_2.unsqueeze(2) - 2 * inner
+    nearest_dis, nearest_index = torch.topk(d_norm_2, k=k, dim=-1, largest=False)
+    if not return_dis:
+        return nearest_index
+    return nearest_index, nearest_dis
+
+
+def indexing_neighbor_chain(x, index):
+    """models/model_utils.py:523-540, line for line (the batch index on x's device)."""
+    batch_size, num_points, k = index.size()
+    id_0 = torch.arange(batch_size, device=x.device).view(-1, 1, 1)
+    x = x.transpose(2, 1).contiguous()
+    feature = x[id_0, index]
+    return feature.permute(0, 3, 1, 2).contiguous()
+
+
+def nearest_distances(x, y):
+    """models/model_utils.py:288-297: x (B,3,N) queries, y (B,3,M) targets -> (B,N,1), the distance of every
+    x point to its nearest y point: sqrt(min_j d_ij), d = ((-2 x.y) + |x|^2) + |y|^2 in torch's fp32 order.
+    Differentiable in x and y.  On fp32 GPU clouds one libpcops scan (pcops_nn_dist_forward) without the
+    (B,N,M) matrix: the minimum is the reference's bit for bit, the square root the correctly rounded one
+    (torch's CPU sqrt is within 1 ulp of it), NaN where the minimum is negative; the gradient is
+    deterministic (pcops_nn_dist_backward).  Anything else runs nearest_distances_chain."""
+    _nn_check(x, y, 1)
+    if not _nn_fused(x, y, 1):
+        return nearest_distances_chain(x, y)
+    return _NNDist.apply(x, y, 1, "A", False, True)[0].unsqueeze(2)
+
+
+def self_nearest_distances(x):
+    """models/model_utils.py:299-307: x (B,3,N) -> (B,N,1), sqrt of the row minimum of the cloud's own
+    distance matrix with 2 ADDED on the diagonal (a point farther than sqrt(2) from every other keeps its
+    own d_ii + 2, with gradient 0).  Fused path and fallbacks as nearest_distances."""
+    _nn_check(x, x, 1)
+    if not _nn_fused(x, x, 1):
+        return self_nearest_distances_chain(x)
+    return _NNDist.apply(x, None, 1, "A", True, True)[0].unsqueeze(2)
+
+
+def self_nearest_distances_K(x, k=3):
+    """models/model_utils.py:309-321: x (B,3,N) -> (B,N,1), sqrt(mean of the k smallest) of the same matrix.
+    The fused path adds the k distances in rank order (torch.mean's order varies with k: within
+    (k + 3) * 2^-24 relative of it on rows of positive terms)."""
+    _nn_check(x, x, k)
+    if not _nn_fused(x, x, k):
+        return self_nearest_distances_K_chain(x, k)
+    return _NNDist.apply(x, None, k, "A", True, True)[0].unsqueeze(2)
+
+
+def get_nearest_index(target, source, k=1, return_dis=False):
+    """models/model_utils.py:501-521: target (B,3,v1), source (B,3,v2) -> the k nearest source points of
+    every target point, int64 (B,v1,k) (with return_dis: also their squared distances (B,v1,k),
+    differentiable in both clouds).  d = (|s|^2 + |t|^2) - 2 t.s in torch's fp32 order; ascending
+    (distance, index) -- torch.topk leaves the order of exact ties unspecified."""
+    _nn_check(target, source, k)
+    if not _nn_fused(target, source, k):
+        return get_nearest_index_chain(target, source, k, return_dis)
+    dis, idx = _NNDist.apply(target, source, k, "B", False, False)
+    return (idx.long(), dis) if return_dis else idx.long()
+
+
+def indexing_neighbor(x, index):
+    """models/model_utils.py:523-540: x (B,C,N0), index (B,N,k) -> (B,C,N,k), x[b, :, index[b, n, j]].
+    fp32 GPU features: grouping_operation; otherwise the reference's indexing."""
+    if _NEIGHBOURS_FUSED and x.is_cuda and index.is_cuda and x.dtype == torch.float32:
+        return grouping_operation(x.contiguous(), index.to(torch.int32).contiguous())
+    return indexing_neighbor_chain(x, index)
+
+
+def knn_chain(x, k):
+    """models/model_utils.py:911-917, line for line."""
+    inner = -2 * torch.matmul(x.transpose(2, 1), x)
+    xx = torch.sum(x ** 2, dim=1, keepdim=True)
+    pairwise_distance = -xx - inner - xx.transpose(2, 1)
+    return pairwise_distance.topk(k=k, dim=-1)[1]
+
+
+def knn(x, k):
+    """models/model_utils.py:911-917: x (B,C,N) -> the k nearest points of every point (itself included),
+    int64 (B,N,k).  On fp32 GPU features the libpcops search (_knn), which ranks by
+    ((-2 dot) + |x_i|^2) + |x_j|^2 where the reference ranks by (inner + |x_j|^2) + |x_i|^2: the order can
+    differ between candidates closer than an ulp of the distance, an order torch.topk leaves unspecified
+    for exact ties anyway."""
+    if not (_NEIGHBOURS_FUSED and x.is_cuda and x.dtype == torch.float32 and k <= NN_DIST_MAX_K):
+        return knn_chain(x, k)
+    pts = x.detach().transpose(1, 2).contiguous()
+    return _knn(pts, pts, k).long()
+
+
+def get_graph_feature(x, k=20, idx=None):
+    """models/model_utils.py:919-943: the DGCNN graph feature [x_j - x_i, x_i] of the k nearest neighbours,
+    x (B,C,N) -> (B,2C,N,k); on x's device (the reference hard-codes 'cuda')."""
+    batch_size = x.size(0)
+    num_points = x.size(2)
+    x = x.view(batch_size, -1, num_points)
+    if idx is None:
+        idx = knn(x, k=k)
+    k = idx.shape[2]
+    feature = indexing_neighbor(x, idx)                       # (B,C,N,k): x_j
+    centre = x.unsqueeze(3).repeat(1, 1, 1, k)
+    return torch.cat((feature - centre, centre), dim=1).contiguous()
+
+
+class MLP(nn.Module):
+    """models/model_utils.py:45-60."""
+
+    def __init__(self, in_channel, layer_dims, bn=None):
+        super().__init__()
+        layers = []
+        last_channel = in_channel
+        for out_channel in layer_dims[:-1]:
+            layers.append(nn.Linear(last_channel, out_channel))
+            if bn:
+                layers.append(nn.BatchNorm1d(out_channel))
+            layers.append(nn.ReLU())
+            last_channel = out_channel
+        layers.append(nn.Linear(last_channel, layer_dims[-1]))
+        self.mlp = nn.Sequential(*layers)
+
+    def forward(self, inputs):
+        return self.mlp(inputs)
+
+
+class MLP_Res(nn.Module):
+    """models/model_utils.py:79-95: x (B,in_dim,n) -> (B,out_dim,n)."""
+
+    def __init__(self, in_dim=128, hidden_dim=None, out_dim=128):
+        super().__init__()
+        if hidden_dim is None:
+            hidden_dim = in_dim
+        self.conv_1 = nn.Conv1d(in_dim, hidden_dim, 1)
+        self.conv_2 = nn.Conv1d(hidden_dim, out_dim, 1)
+        self.conv_shortcut = nn.Conv1d(in_dim, out_dim, 1)
+
+    def forward(self, x):
+        shortcut = self.conv_shortcut(x)
+        return self.conv_2(torch.relu(self.conv_1(x))) + shortcut
+
+
+class PointNetFeatureExtractor(nn.Module):
+    """models/model_utils.py:631-805: the PointNet feature extractor (global, or per-point with the
+    global feature repeated); x (B,N,D), or (B,D,N) with transposed_input."""
+
+    def __init__(self, in_channels=3, feat_size=1024, layer_dims=[64, 128], global_feat=True,
+                 activation=torch.nn.functional.relu, batchnorm=True, transposed_input=False):
+        super().__init__()
+        if not isinstance(in_channels, int):
+            raise TypeError(f"Argument in_channels expected to be of type int. Got {type(in_channels)} instead.")
+        if not isinstance(feat_size, int):
+            raise TypeError(f"Argument feat_size expected to be of type int. Got {type(feat_size)} instead.")
+        if not hasattr(layer_dims, "__iter__"):
+            raise TypeError("Argument layer_dims is not iterable.")
+        for i, layer_dim in enumerate(layer_dims):
+            if not isinstance(layer_dim, int):
+                raise TypeError(f"Elements of layer_dims must be of type int. Found type {type(layer_dim)} at index {i}.")
+        if not isinstance(global_feat, bool):
+            raise TypeError(f"Argument global_feat expected to be of type bool. Got {type(global_feat)} instead.")
+        self.feat_size = feat_size
+        self.activation = activation
+        self.global_feat = global_feat
+        dims = [in_channels] + list(layer_dims) + [feat_size]   # the caller's list is left as it is
+        self.conv_layers = nn.ModuleList()
+        if batchnorm:
+            self.bn_layers = nn.ModuleList()
+        for i in range(len(dims) - 1):
+            self.conv_layers.append(nn.Conv1d(dims[i], dims[i + 1], 1))
+            if batchnorm:
+                self.bn_layers.append(nn.BatchNorm1d(dims[i + 1]))
+        self.batchnorm = batchnorm
+        self.transposed_input = transposed_input
+
+    def _layer(self, i, x):
+        x = self.conv_layers[i](x)
+        return self.bn_layers[i](x) if self.batchnorm else x
+
+    def forward(self, x):
+        if not self.transposed_input:
+            x = x.transpose(1, 2)
+        num_points = x.shape[2]
+        x = self.activation(self._layer(0, x))
+        local_features = x if self.global_feat is False else None
+        for i in range(1, len(self.conv_layers) - 1):
+            x = self.activation(self._layer(i, x))
+        x = self._layer(len(self.conv_layers) - 1, x)     # the last layer: no nonlinearity
+        x = torch.max(x, 2, keepdim=True)[0]
+        x = x.view(-1, self.feat_size)
+        if self.global_feat:
+            return x
+        x = x.view(-1, self.feat_size, 1).repeat(1, 1, num_points)
+        return torch.cat((x, local_features), dim=1)

@@ -272,6 +272,41 @@ int pcops_chamfer_backward(const float *xyz1, const float *xyz2, int B, int N, i
 int pcops_chamfer_sqrt_mean_grad(const float *grad_out, float scale, const float *s1, long long n1, const float *s2,
                                  long long n2, float *gd1, float *gd2, pcops_stream_t stream);
 
+/* ---------------- Chamfer over clouds of unequal size ("counted" clouds) ----------------
+ * xyz1 (B,N,3) / xyz2 (B,M,3) are padded buffers; cloud b holds counts1[b] / counts2[b] points
+ * (device int32, clamped to [0,N] / [0,M]; a NULL counts pointer means that side is full; both NULL
+ * returns PCOPS_ERR_INVALID -- use the uniform entry).  Row k >= count is ABSENT whatever it holds
+ * (zeros, NaN, inf): never a query, never a target.  The counts are read on the device only.
+ *   pcops_chamfer_forward_counts: for its valid rows cloud pair b gets exactly what
+ *     pcops_chamfer_forward gives for (xyz1[b, :c1], xyz2[b, :c2]) at B = 1 -- distance bits, lowest
+ *     index on ties, the reference's scan order on non-finite data; absent rows get dist = 0,
+ *     idx = 0, and so does every row of a pair with an empty side.  One launch, both directions;
+ *     direct or screened search chosen from B, N, M alone (no culled form: no workspace).
+ *   pcops_chamfer_backward_counts: pcops_chamfer_backward's scheme (every row written once, 64-bit
+ *     fixed-point partner sums: bitwise reproducible) with the source scan and the target ranges cut
+ *     at the counts and the fixed-point scale taken over valid terms.  graddist of an absent row is
+ *     never read (NaN there is harmless); absent rows and pairs with an empty side get zero rows.
+ *   pcops_chamfer_counts_means: out (B,4) = per pair (mean sqrt dist1, mean sqrt dist2, mean dist1,
+ *     mean dist2) over the valid rows, in pcops_completion_metrics' fixed summation order (the same
+ *     bits as that row's l1a, l1b, l2a, l2b); zeros for a pair with an empty side.
+ *   pcops_chamfer_counts_mean_grad: d(loss)/d(dist) of loss = mean_b l_b, l_b the reference's
+ *     Chamfer loss of pair b, from grad_out (one float on the device) and the SQUARED distances:
+ *       gd[b,i] = ((g * scale) * (1 / B)) * (1 / c[b])              root == 0
+ *       gd[b,i] = ((g * scale) * (1 / B)) * (1 / c[b]) / (2 sqrt d) root != 0
+ *     0 on absent rows and on pairs with an empty side; both == 0: gd2 = 0 (single-sided losses,
+ *     dist2 may be NULL).  Feeds pcops_chamfer_backward_counts. */
+int pcops_chamfer_forward_counts(const float *xyz1, const float *xyz2, const int *counts1, const int *counts2, int B,
+                                 int N, int M, float *dist1, float *dist2, int *idx1, int *idx2,
+                                 pcops_stream_t stream);
+int pcops_chamfer_backward_counts(const float *xyz1, const float *xyz2, const int *counts1, const int *counts2, int B,
+                                  int N, int M, const float *graddist1, const float *graddist2, const int *idx1,
+                                  const int *idx2, float *gradxyz1, float *gradxyz2, pcops_stream_t stream);
+int pcops_chamfer_counts_means(const float *dist1, const float *dist2, const int *counts1, const int *counts2, int B,
+                               int N, int M, float *out, pcops_stream_t stream);
+int pcops_chamfer_counts_mean_grad(const float *grad_out, float scale, const float *dist1, const float *dist2,
+                                   const int *counts1, const int *counts2, int B, int N, int M, int root, int both,
+                                   float *gd1, float *gd2, pcops_stream_t stream);
+
 /* ---------------- Completion metrics (utils/loss_utils.py:98-155, metrics/CD/fscore.py:3-16) ----------------
  * pcops_completion_metrics: what calc_cd(output, gt, calc_f1=True) and calc_dcd(output, gt, alpha, n_lambda=1)
  * compute per sample from ONE Chamfer result chamfer(gt, output), in one launch.
@@ -309,6 +344,17 @@ unsigned long long pcops_completion_metrics_workspace_bytes(int B, int N, int M)
 int pcops_completion_metrics(const float *dist1, const int *idx1, const float *dist2, const int *idx2, int B, int N,
                              int M, float threshold, float alpha, float frac1, float frac2, float *out,
                              void *workspace, unsigned long long workspace_bytes, pcops_stream_t stream);
+/* pcops_completion_metrics_counts: the same 12 columns for counted clouds (see "Chamfer over clouds
+ * of unequal size"): dist1 / idx1 strided by N with counts1[b] valid rows, dist2 / idx2 by M with
+ * counts2[b]; per pair n = counts1[b], m = counts2[b] replace N and M everywhere -- the means, the
+ * hit-count bins (valid targets only) and the density fractions frac1 = fp32(double(n) / double(m)),
+ * frac2 = fp32(double(m) / double(n)), max(1, .) of them when non_reg != 0.  A pair with an empty
+ * side gets an all-NaN row.  workspace: pcops_completion_metrics_workspace_bytes of the padded
+ * (B, N, M).  B == 0 returns PCOPS_OK; both counts NULL returns PCOPS_ERR_INVALID. */
+int pcops_completion_metrics_counts(const float *dist1, const int *idx1, const float *dist2, const int *idx2,
+                                    const int *counts1, const int *counts2, int B, int N, int M, float threshold,
+                                    float alpha, int non_reg, float *out, void *workspace,
+                                    unsigned long long workspace_bytes, pcops_stream_t stream);
 
 /* ---------------- 3x3 / stride 2 / pad 1 max pool (torchvision resnet stem, PointSea ResEncoder)
  * pcops_maxpool3s2_fwd: nn.MaxPool2d(3, 2, 1) on a channels_last (N, H, W, C) activation (dtype 0

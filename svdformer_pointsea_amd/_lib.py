@@ -54,6 +54,11 @@ _SIGS = {
     "pcops_chamfer_forward_ws": (I, [P, P, I, I, I, P, P, P, P, P, ULL, P]),
     "pcops_chamfer_backward": (I, [P, P, I, I, I, P, P, P, P, P, P, P]),
     "pcops_chamfer_sqrt_mean_grad": (I, [P, F, P, LL, P, LL, P, P, P]),
+    "pcops_chamfer_forward_counts": (I, [P, P, P, P, I, I, I, P, P, P, P, P]),
+    "pcops_chamfer_backward_counts": (I, [P, P, P, P, I, I, I, P, P, P, P, P, P, P]),
+    "pcops_chamfer_counts_means": (I, [P, P, P, P, I, I, I, P, P]),
+    "pcops_chamfer_counts_mean_grad": (I, [P, F, P, P, P, P, I, I, I, I, I, P, P, P]),
+    "pcops_completion_metrics_counts": (I, [P, P, P, P, P, P, I, I, I, F, F, I, P, P, ULL, P]),
     "pcops_completion_metrics_workspace_bytes": (ULL, [I, I, I]),
     "pcops_completion_metrics": (I, [P, P, P, P, I, I, I, F, F, F, F, P, P, ULL, P]),
     "pcops_maxpool3s2_fwd": (I, [P, I, I, I, I, I, P, P, P]),

@@ -74,20 +74,43 @@ __device__ __forceinline__ bool finite3(float x, float y, float z) {
   return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;
 }
 
-template <int Q>
+// Counted clouds (pcops_chamfer_forward_counts): the direct and the screened kernel carry a template
+// flag, as the FPS kernels do -- CNT = false is the uniform instantiation (cnt1 / cnt2 unused, the
+// same code as without the flag), CNT = true reads the counts.  There NAp / NTp are the padded row
+// counts (the strides), NA / NT the clouds' own counts clamped to [0, padded]; a row k >= count is
+// absent: never read as a query or a target, written (0, 0).  A pair with an empty side is all (0, 0).
+template <bool CNT>
+__device__ __forceinline__ int cloud_count(const int *cnt, int b, int n) {
+  return (CNT && cnt) ? min(max(cnt[b], 0), n) : n;
+}
+
+// the block's rows [q0, q0 + rows) of a counted cloud that need no search: (0, 0)
+__device__ __forceinline__ void write_absent(float *dist, int *idx, int q0, int rows, int NAp) {
+  for (int q = q0 + threadIdx.x; q < min(q0 + rows, NAp); q += blockDim.x) dist[q] = 0.f, idx[q] = 0;
+}
+
+template <int Q, bool CNT = false>
 __global__ __launch_bounds__(kThreads) void chamfer_nn_kernel(const float *__restrict__ xyz1,
                                                               const float *__restrict__ xyz2, int N, int M,
                                                               float *__restrict__ dist1, float *__restrict__ dist2,
                                                               int *__restrict__ idx1, int *__restrict__ idx2,
-                                                              int blocks_dir0) {
+                                                              int blocks_dir0, const int *__restrict__ cnt1 = nullptr,
+                                                              const int *__restrict__ cnt2 = nullptr) {
   const int b = blockIdx.y;
   const bool dir = (int)blockIdx.x >= blocks_dir0;
   const int bx = dir ? blockIdx.x - blocks_dir0 : blockIdx.x;
-  const int NA = dir ? M : N, NT = dir ? N : M;
-  const float *A = (dir ? xyz2 : xyz1) + (size_t)b * NA * 3;
-  const float *T = (dir ? xyz1 : xyz2) + (size_t)b * NT * 3;
-  float *dist = (dir ? dist2 : dist1) + (size_t)b * NA;
-  int *idx = (dir ? idx2 : idx1) + (size_t)b * NA;
+  const int NAp = dir ? M : N, NTp = dir ? N : M;
+  const int NA = cloud_count<CNT>(dir ? cnt2 : cnt1, b, NAp), NT = cloud_count<CNT>(dir ? cnt1 : cnt2, b, NTp);
+  const float *A = (dir ? xyz2 : xyz1) + (size_t)b * NAp * 3;
+  const float *T = (dir ? xyz1 : xyz2) + (size_t)b * NTp * 3;
+  float *dist = (dir ? dist2 : dist1) + (size_t)b * NAp;
+  int *idx = (dir ? idx2 : idx1) + (size_t)b * NAp;
+  if (CNT) {
+    if (NT <= 0 || bx * kThreads * Q >= NA) {  // empty side, or a block of absent rows only
+      write_absent(dist, idx, bx * kThreads * Q, kThreads * Q, NAp);
+      return;
+    }
+  }
   if (NT <= 0) return;  // outputs keep the caller's zeros (chamfer3D.cu never writes them)
   const bool nanst = nan_chunk_starts(T, NT);
 
@@ -144,7 +167,10 @@ __global__ __launch_bounds__(kThreads) void chamfer_nn_kernel(const float *__res
 #pragma unroll
   for (int i = 0; i < Q; ++i) {
     const int qi = bx * kThreads * Q + i * kThreads + tid;
-    if (qi >= NA) continue;
+    if (qi >= NA) {
+      if (CNT && qi < NAp) dist[qi] = 0.f, idx[qi] = 0;
+      continue;
+    }
     if (nanst || !finite3(ax[i], ay[i], az[i])) {
       float r = 0.f;
       int rk = 0;
@@ -199,20 +225,29 @@ __device__ __forceinline__ float screen_slack(float mine, float an, float eps) {
   return 2.f * eps + 16.f * kU * fmaxf(0.f, mine + an + eps);
 }
 
-template <int Q>
+template <int Q, bool CNT = false>   // CNT: see chamfer_nn_kernel
 __global__ __launch_bounds__(kThreads) void chamfer_screen_kernel(const float *__restrict__ xyz1,
                                                                   const float *__restrict__ xyz2, int N, int M,
                                                                   float *__restrict__ dist1, float *__restrict__ dist2,
                                                                   int *__restrict__ idx1, int *__restrict__ idx2,
-                                                                  int blocks_dir0) {
+                                                                  int blocks_dir0,
+                                                                  const int *__restrict__ cnt1 = nullptr,
+                                                                  const int *__restrict__ cnt2 = nullptr) {
   const int b = blockIdx.y;
   const bool dir = (int)blockIdx.x >= blocks_dir0;
   const int bx = dir ? blockIdx.x - blocks_dir0 : blockIdx.x;
-  const int NA = dir ? M : N, NT = dir ? N : M;
-  const float *A = (dir ? xyz2 : xyz1) + (size_t)b * NA * 3;
-  const float *T = (dir ? xyz1 : xyz2) + (size_t)b * NT * 3;
-  float *dist = (dir ? dist2 : dist1) + (size_t)b * NA;
-  int *idx = (dir ? idx2 : idx1) + (size_t)b * NA;
+  const int NAp = dir ? M : N, NTp = dir ? N : M;
+  const int NA = cloud_count<CNT>(dir ? cnt2 : cnt1, b, NAp), NT = cloud_count<CNT>(dir ? cnt1 : cnt2, b, NTp);
+  const float *A = (dir ? xyz2 : xyz1) + (size_t)b * NAp * 3;
+  const float *T = (dir ? xyz1 : xyz2) + (size_t)b * NTp * 3;
+  float *dist = (dir ? dist2 : dist1) + (size_t)b * NAp;
+  int *idx = (dir ? idx2 : idx1) + (size_t)b * NAp;
+  if (CNT) {
+    if (NT <= 0 || bx * kThreads * Q >= NA) {  // empty side, or a block of absent rows only
+      write_absent(dist, idx, bx * kThreads * Q, kThreads * Q, NAp);
+      return;
+    }
+  }
   if (NT <= 0) return;
   const bool nanst = nan_chunk_starts(T, NT);
 
@@ -425,7 +460,10 @@ __global__ __launch_bounds__(kThreads) void chamfer_screen_kernel(const float *_
 #pragma unroll
   for (int i = 0; i < Q; ++i) {
     const int qi = bx * kThreads * Q + i * kThreads + tid;
-    if (qi >= NA) continue;
+    if (qi >= NA) {
+      if (CNT && qi < NAp) dist[qi] = 0.f, idx[qi] = 0;
+      continue;
+    }
     const float best = bestv[i];
     const int bk = bkv[i];
     dist[qi] = (raw[i] || best < INFINITY) ? best
@@ -664,10 +702,17 @@ __global__ void chamfer_grad_partner_kernel(const float *__restrict__ xyz1, cons
 constexpr int kGThreads = 512;
 constexpr int kGTargets = 2048;   // targets per block at most: 2048 x (3 x 8 + 4) B = 56 KB of LDS
 
+// CNT (pcops_chamfer_backward_counts; CNT = false is the uniform instantiation, cnt1 / cnt2 unused): the
+// target ranges are cut from the padded row count NTp -- the grid cannot depend on a count the host
+// never reads -- and stop at the target cloud's count; the source scan stops at the source count,
+// so the scale 2^sh is set by valid terms only and an absent row's incoming gradient is never
+// read.  Absent rows of a range, and every row of a pair with an empty side, get a zero gradient.
+template <bool CNT = false>
 __global__ __launch_bounds__(kGThreads) void chamfer_grad_seg_kernel(
     const float *__restrict__ xyz1, const float *__restrict__ xyz2, int N, int M, const float *__restrict__ gd1,
     const float *__restrict__ gd2, const int *__restrict__ idx1, const int *__restrict__ idx2, float *__restrict__ g1,
-    float *__restrict__ g2, int parts0, int parts1) {
+    float *__restrict__ g2, int parts0, int parts1, const int *__restrict__ cnt1 = nullptr,
+    const int *__restrict__ cnt2 = nullptr) {
   __shared__ long long acc[kGTargets * 3];
   __shared__ int flags[kGTargets];
   __shared__ float red[kGThreads / 64];
@@ -682,16 +727,20 @@ __global__ __launch_bounds__(kGThreads) void chamfer_grad_seg_kernel(
   const bool dir = x >= parts0;
   const int part = dir ? x - parts0 : x;
   const int parts = dir ? parts1 : parts0;
-  const int NA = dir ? M : N, NT = dir ? N : M;
-  const float *S = (dir ? xyz2 : xyz1) + (size_t)b * NA * 3;
-  const float *T = (dir ? xyz1 : xyz2) + (size_t)b * NT * 3;
-  const float *gS = (dir ? gd2 : gd1) + (size_t)b * NA;
-  const int *iS = (dir ? idx2 : idx1) + (size_t)b * NA;
-  const float *gT = (dir ? gd1 : gd2) + (size_t)b * NT;
-  const int *iT = (dir ? idx1 : idx2) + (size_t)b * NT;
-  float *out = (dir ? g1 : g2) + (size_t)b * NT * 3;
-  const int R = (NT + parts - 1) / parts;
-  const int j0 = part * R, j1 = min(NT, j0 + R);
+  const int NAp = dir ? M : N, NTp = dir ? N : M;
+  const int NA = cloud_count<CNT>(dir ? cnt2 : cnt1, b, NAp), NT = cloud_count<CNT>(dir ? cnt1 : cnt2, b, NTp);
+  const float *S = (dir ? xyz2 : xyz1) + (size_t)b * NAp * 3;
+  const float *T = (dir ? xyz1 : xyz2) + (size_t)b * NTp * 3;
+  const float *gS = (dir ? gd2 : gd1) + (size_t)b * NAp;
+  const int *iS = (dir ? idx2 : idx1) + (size_t)b * NAp;
+  const float *gT = (dir ? gd1 : gd2) + (size_t)b * NTp;
+  const int *iT = (dir ? idx1 : idx2) + (size_t)b * NTp;
+  float *out = (dir ? g1 : g2) + (size_t)b * NTp * 3;
+  const int R = (NTp + parts - 1) / parts;
+  const int j0 = part * R, j1 = min(NA > 0 || !CNT ? NT : 0, j0 + R);
+  if (CNT) {  // the range's absent rows (all of them when either side is empty)
+    for (int e = max(j0, j1) * 3 + tid; e < min(NTp, j0 + R) * 3; e += kGThreads) out[e] = 0.f;
+  }
   if (j0 >= j1) return;
 
   // pass 1: the largest finite |partner term| of this block's targets
@@ -1386,7 +1435,7 @@ extern "C" int pcops_chamfer_backward(const float *xyz1, const float *xyz2, int 
       return p;
     };
     const int p0 = parts_for(M), p1 = parts_for(N);
-    hipLaunchKernelGGL(chamfer_grad_seg_kernel, dim3((unsigned)((long)(p0 + p1) * B)), dim3(kGThreads), 0, s, xyz1,
+    hipLaunchKernelGGL(chamfer_grad_seg_kernel<>, dim3((unsigned)((long)(p0 + p1) * B)), dim3(kGThreads), 0, s, xyz1,
                        xyz2, N, M, graddist1, graddist2, idx1, idx2, gradxyz1, gradxyz2, p0, p1);
     PC_CHECK_LAUNCH();
     return PCOPS_OK;
@@ -1399,6 +1448,140 @@ extern "C" int pcops_chamfer_backward(const float *xyz1, const float *xyz2, int 
   PC_CHECK_LAUNCH();
   hipLaunchKernelGGL(chamfer_grad_partner_kernel, dim3(grid), dim3(256), 0, s, xyz1, xyz2, B, N, M, graddist1,
                      graddist2, idx1, idx2, gradxyz1, gradxyz2);
+  PC_CHECK_LAUNCH();
+  return PCOPS_OK;
+}
+
+// ---------------------------------------------------------------- counted clouds
+// Clouds of unequal size in one batch: (B, N, 3) / (B, M, 3) buffers whose cloud b holds counts1[b] /
+// counts2[b] points (device int32, clamped to [0, N] / [0, M]; a null pointer = that side is full).
+// For its valid rows pair b gets what pcops_chamfer_forward gives (xyz1[b, :c1], xyz2[b, :c2]) --
+// the same bodies, swept to the count -- and absent rows get (0, 0).  The counts are read by the
+// kernels only: the grid is cut from N and M, so the dispatch depends on B, N and M alone, and a
+// block whose queries are all absent ends after writing the padding.  Direct or screened search
+// (PCOPS_CHAMFER_SCREEN / PCOPS_CHAMFER_Q as in pcops_chamfer_forward); no MFMA and no culled form.
+extern "C" int pcops_chamfer_forward_counts(const float *xyz1, const float *xyz2, const int *counts1,
+                                            const int *counts2, int B, int N, int M, float *dist1, float *dist2,
+                                            int *idx1, int *idx2, pcops_stream_t stream) {
+  if (B < 0 || N < 0 || M < 0) return PCOPS_ERR_INVALID;
+  if (B == 0 || (N == 0 && M == 0)) return PCOPS_OK;
+  if (!counts1 && !counts2) return PCOPS_ERR_INVALID;
+  if (!xyz1 || !xyz2 || (N && (!dist1 || !idx1)) || (M && (!dist2 || !idx2))) return PCOPS_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  if (N == 0 || M == 0) {
+    if (N && (pc_memset_async(dist1, 0, sizeof(float) * B * N, s) || pc_memset_async(idx1, 0, sizeof(int) * B * N, s)))
+      return PCOPS_ERR_LAUNCH;
+    if (M && (pc_memset_async(dist2, 0, sizeof(float) * B * M, s) || pc_memset_async(idx2, 0, sizeof(int) * B * M, s)))
+      return PCOPS_ERR_LAUNCH;
+    return PCOPS_OK;
+  }
+  auto blocks = [&](int q) {
+    return (long)B * (((N + kThreads * q - 1) / (kThreads * q)) + ((M + kThreads * q - 1) / (kThreads * q)));
+  };
+  int Q = blocks(4) >= 1024 ? 4 : 1;   // pcops_chamfer_forward's rule
+  if (const char *e = getenv("PCOPS_CHAMFER_Q")) Q = atoi(e);
+  const char *se = getenv("PCOPS_CHAMFER_SCREEN");
+  const bool screen = !(se && se[0] == '0');
+  if (Q != 1 && Q != 2 && Q != 4 && !(Q == 8 && !screen)) Q = 1;
+  const int b0 = (N + kThreads * Q - 1) / (kThreads * Q);
+  const int b1 = (M + kThreads * Q - 1) / (kThreads * Q);
+  const dim3 grid(b0 + b1, B);
+#define PC_CH_CNT(KERNEL, QQ)                                                                                 \
+  hipLaunchKernelGGL((KERNEL<QQ, true>), grid, dim3(kThreads), 0, s, xyz1, xyz2, N, M, dist1, dist2, idx1, idx2, \
+                     b0, counts1, counts2)
+  if (screen && Q == 4)
+    PC_CH_CNT(chamfer_screen_kernel, 4);
+  else if (screen && Q == 2)
+    PC_CH_CNT(chamfer_screen_kernel, 2);
+  else if (screen)
+    PC_CH_CNT(chamfer_screen_kernel, 1);
+  else if (Q == 8)
+    PC_CH_CNT(chamfer_nn_kernel, 8);
+  else if (Q == 4)
+    PC_CH_CNT(chamfer_nn_kernel, 4);
+  else if (Q == 2)
+    PC_CH_CNT(chamfer_nn_kernel, 2);
+  else
+    PC_CH_CNT(chamfer_nn_kernel, 1);
+#undef PC_CH_CNT
+  PC_CHECK_LAUNCH();
+  return PCOPS_OK;
+}
+
+// pcops_chamfer_backward over counted clouds: chamfer_grad_seg_kernel's scheme (bitwise
+// reproducible), see chamfer_grad_seg_kernel.  graddist rows of absent points are never read.
+extern "C" int pcops_chamfer_backward_counts(const float *xyz1, const float *xyz2, const int *counts1,
+                                             const int *counts2, int B, int N, int M, const float *graddist1,
+                                             const float *graddist2, const int *idx1, const int *idx2,
+                                             float *gradxyz1, float *gradxyz2, pcops_stream_t stream) {
+  if (B < 0 || N < 0 || M < 0) return PCOPS_ERR_INVALID;
+  if (B == 0 || (N == 0 && M == 0)) return PCOPS_OK;
+  if (!counts1 && !counts2) return PCOPS_ERR_INVALID;
+  hipStream_t s = (hipStream_t)stream;
+  if (N == 0 || M == 0) {
+    if ((N && !gradxyz1) || (M && !gradxyz2)) return PCOPS_ERR_INVALID;
+    if (N && pc_memset_async(gradxyz1, 0, sizeof(float) * 3 * B * N, s)) return PCOPS_ERR_LAUNCH;
+    if (M && pc_memset_async(gradxyz2, 0, sizeof(float) * 3 * B * M, s)) return PCOPS_ERR_LAUNCH;
+    return PCOPS_OK;
+  }
+  if (!xyz1 || !xyz2 || !graddist1 || !graddist2 || !idx1 || !idx2 || !gradxyz1 || !gradxyz2)
+    return PCOPS_ERR_INVALID;
+  auto parts_for = [&](int NT) {   // pcops_chamfer_backward's rule, on the padded sizes
+    int p = (NT + kGTargets - 1) / kGTargets;
+    while ((long)B * 2 * p < 512 && (NT + 2 * p - 1) / (2 * p) >= 512) p *= 2;
+    return p;
+  };
+  const int p0 = parts_for(M), p1 = parts_for(N);
+  hipLaunchKernelGGL(chamfer_grad_seg_kernel<true>, dim3((unsigned)((long)(p0 + p1) * B)), dim3(kGThreads), 0, s, xyz1,
+                     xyz2, N, M, graddist1, graddist2, idx1, idx2, gradxyz1, gradxyz2, p0, p1, counts1, counts2);
+  PC_CHECK_LAUNCH();
+  return PCOPS_OK;
+}
+
+// d(loss)/d(dist) of the counted Chamfer losses, loss = mean_b l_b with l_b the reference's loss on
+// cloud pair b cut to its counts, in one launch: t = g * scale (0.5 for chamfer_sqrt's "/ 2", else
+// 1), t * (1 / B), t * (1 / c[b]), then / (2 sqrt(d)) when root -- autograd's order for the chain of
+// B = 1 calls.  0 on absent rows, on a pair with an empty side, and on all of direction 2 when
+// !both (single-sided losses).  d1 / d2 are the SQUARED distances of the counted forward.
+namespace {
+__global__ void chamfer_counts_mean_grad_kernel(const float *__restrict__ go, float scale, float inv_b,
+                                                const float *__restrict__ d1, const float *__restrict__ d2,
+                                                const int *__restrict__ cnt1, const int *__restrict__ cnt2, int N,
+                                                int M, long long n1, long long n2, int root, int both,
+                                                float *__restrict__ gd1, float *__restrict__ gd2) {
+  const float t = go[0] * scale * inv_b;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n1 + n2; i += stride) {
+    const bool dir = i >= n1;
+    const long long e = dir ? i - n1 : i;
+    const int NAp = dir ? M : N;
+    const int b = (int)(e / NAp), k = (int)(e - (long long)b * NAp);
+    const int c1 = cloud_count<true>(cnt1, b, N), c2 = cloud_count<true>(cnt2, b, M);
+    const int ca = dir ? c2 : c1;
+    float v = 0.f;
+    if (k < ca && c1 > 0 && c2 > 0 && (!dir || both)) {
+      v = t * (1.0f / (float)ca);
+      if (root) v = v / (2.f * sqrtf((dir ? d2 : d1)[e]));
+    }
+    (dir ? gd2 : gd1)[e] = v;
+  }
+}
+}  // namespace
+
+extern "C" int pcops_chamfer_counts_mean_grad(const float *grad_out, float scale, const float *dist1,
+                                              const float *dist2, const int *counts1, const int *counts2, int B,
+                                              int N, int M, int root, int both, float *gd1, float *gd2,
+                                              pcops_stream_t stream) {
+  if (B < 0 || N < 0 || M < 0) return PCOPS_ERR_INVALID;
+  const long long n1 = (long long)B * N, n2 = (long long)B * M;
+  if (n1 + n2 == 0) return PCOPS_OK;
+  if (!counts1 && !counts2) return PCOPS_ERR_INVALID;
+  if (!grad_out || (n1 && (!dist1 || !gd1)) || (n2 && (!gd2 || (both && !dist2)))) return PCOPS_ERR_INVALID;
+  long long blocks = (n1 + n2 + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(chamfer_counts_mean_grad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                     grad_out, scale, 1.0f / (float)B, dist1, dist2, counts1, counts2, N, M, n1, n2, root, both, gd1,
+                     gd2);
   PC_CHECK_LAUNCH();
   return PCOPS_OK;
 }

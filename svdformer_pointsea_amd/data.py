@@ -62,7 +62,7 @@ def _crop_pack(dist, xyz, start, count, n_max):
 
 
 def seprate_point_cloud(xyz, num_points, crop, fixed_points=None, padding_zeros=False, generator=None,
-                        want_crop=True, centers=None):
+                        want_crop=True, centers=None, return_counts=False):
     """utils/helpers.py:62-123 -> (input_data, crop_data).
 
     crop: int, or [lo, hi] for a per-sample random crop size (then both parts
@@ -75,7 +75,10 @@ def seprate_point_cloud(xyz, num_points, crop, fixed_points=None, padding_zeros=
     no random numbers, so input_data is unchanged.
     centers (optional, a (B, 3) tensor): sample b's crop centre, instead of a draw or of
     fixed_points -- the ShapeNet-55 test protocol's fixed viewpoints for a whole batch of
-    (shape, view) pairs at once (core/test_55.py:71-72 calls this per view at B = 1)."""
+    (shape, view) pairs at once (core/test_55.py:71-72 calls this per view at B = 1).
+    return_counts=True (a crop range, CUDA fp32, the fused packing): two more values, the packed input
+    cloud BEFORE its FPS subsampling -- (B, n - crop[0], 3), every point the crop left, zero rows past
+    each cloud's count -- and its counts (B,) int32: what metrics.get_loss_PM(..., partial_counts=) takes."""
     B, n, c = xyz.shape
     assert n == num_points
     assert c == 3
@@ -122,8 +125,11 @@ def seprate_point_cloud(xyz, num_points, crop, fixed_points=None, padding_zeros=
                 return fps_subsample(cloud.contiguous(), 2048)
             return fps_subsample_counts(cloud.contiguous(), count.to(torch.int32) if count32 is None else count32, 2048)
 
+        if return_counts and not fused:
+            raise RuntimeError("seprate_point_cloud: return_counts needs CUDA fp32 clouds and the fused crop packing")
+        extra = (input_data, in_counts) if return_counts else ()
         if not want_crop:
-            return fps(input_data, n - num_crop, in_counts), None
+            return (fps(input_data, n - num_crop, in_counts), None) + extra
         cr_counts = None
         if fused:
             crop_data, cr_counts = _crop_pack(dist, xyz, torch.zeros_like(num_crop), num_crop, hi)
@@ -134,7 +140,9 @@ def seprate_point_cloud(xyz, num_points, crop, fixed_points=None, padding_zeros=
         with fork(dev, inputs=(crop_data, num_crop) + ((cr_counts,) if cr_counts is not None else ())) as br:
             crop_out = fps(crop_data, num_crop, cr_counts)
         input_out = fps(input_data, n - num_crop, in_counts)
-        return input_out, br.join(crop_out)
+        return (input_out, br.join(crop_out)) + extra
+    if return_counts:
+        raise RuntimeError("seprate_point_cloud: return_counts needs a crop range [lo, hi]")
     k = int(crop)
     if not padding_zeros:
         input_data = torch.gather(xyz, 1, order[:, k:].unsqueeze(-1).expand(B, n - k, 3))
